@@ -9,6 +9,14 @@ the prelim consensus (device pileup), ONE remap iteration (--local mapping
 against the consensus, device pileup, consensus + distance filter).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs).  --full adds the legs beyond the headline
+figure, untimed: the CPU baseline, the parity legs and the end-to-end
+(file to file) legs; --no-cpu-baseline, --no-parity, --no-e2e and
+--parity-full CHUNK select among them.
 
 N > 1 is launched by torch.distributed.run, one rank per GPU; every rank holds
 its own block of P pairs (weak scaling), per-reference tallies and the dense
@@ -153,6 +161,58 @@ def cpu_baseline(reads, quals, paired=True, iterations=1, forced=False, workload
                       'faster; reads packed before timing'.format(
                           units, 'pairs' if paired else 'reads', workload, passes, allc, runs[allc],
                           share, runs[share])}, prep.result
+
+
+DUMP_BLOCKS = 64           # --dump-outputs: seeded blocks of alignment records ...
+DUMP_BLOCK_RECORDS = 512   # ... of this many records each (38.8 MB as float64)
+
+
+def dump_outputs(dirname, ctx, conseqs, new_counts, unmapped):
+    """What the last timed step handed its caller, as DIR/<name>.npy
+    (float32 / float64, under 64 MB in all):
+
+      conseq_names.txt   the consensus names, one per line, in the order of
+                         the arrays below (the only file that is not .npy)
+      conseq_<k>.npy     float32 [len]: the character codes of the k-th
+                         consensus RemapPipeline.run returned
+      mapped_counts.npy  float64 [K]: its mapped-line count per consensus
+      unmapped.npy       float64 [1]: its unmapped-line count
+      records_index.npy  float64 [n]: the read index of every sampled record
+      records.npy        float64 [n, 20 + MAXOPS]: the last mapping pass's
+                         alignment records (Context.fetch) of those reads,
+                         ALN_FIELDS then the CIGAR words, the words past
+                         n_cigar (unspecified in the record) set to 0
+
+    The records are all of them when they fit, else DUMP_BLOCKS blocks of
+    DUMP_BLOCK_RECORDS consecutive reads at starts drawn with SEED: the same
+    reads in every run with the same arguments."""
+    from micall_amd import _native
+    os.makedirs(dirname, exist_ok=True)
+    names = list(conseqs)
+    with open(os.path.join(dirname, 'conseq_names.txt'), 'w') as f:
+        f.write(''.join(n + '\n' for n in names))
+    for k, n in enumerate(names):
+        np.save(os.path.join(dirname, 'conseq_%d.npy' % k),
+                np.frombuffer(conseqs[n].encode(), dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(dirname, 'mapped_counts.npy'),
+            np.asarray([new_counts.get(n, 0) for n in names], dtype=np.float64))
+    np.save(os.path.join(dirname, 'unmapped.npy'), np.asarray([unmapped], dtype=np.float64))
+    n_reads = ctx.reads_count()[0]
+    if n_reads <= DUMP_BLOCKS * DUMP_BLOCK_RECORDS:
+        blocks = [(0, n_reads)]
+    else:
+        slots = n_reads // DUMP_BLOCK_RECORDS
+        starts = np.sort(np.random.default_rng(SEED).choice(slots, DUMP_BLOCKS, replace=False))
+        blocks = [(int(a) * DUMP_BLOCK_RECORDS, DUMP_BLOCK_RECORDS) for a in starts]
+    index = np.concatenate([np.arange(a, a + n, dtype=np.float64) for a, n in blocks])
+    rec = np.concatenate([ctx.fetch(a, n) for a, n in blocks])
+    out = np.empty((len(rec), len(_native.ALN_FIELDS) + rec['cigar'].shape[1]), dtype=np.float64)
+    for j, f in enumerate(_native.ALN_FIELDS):
+        out[:, j] = rec[f]
+    live = np.arange(rec['cigar'].shape[1])[None, :] < rec['n_cigar'][:, None]
+    out[:, len(_native.ALN_FIELDS):] = np.where(live, rec['cigar'], 0)
+    np.save(os.path.join(dirname, 'records_index.npy'), index)
+    np.save(os.path.join(dirname, 'records.npy'), out)
 
 
 def record_mismatches(dev, ref):
@@ -1362,6 +1422,13 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--pairs', type=int, default=1000000, help='read pairs per GPU')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last step computed (consensus '
+                         'sequences, mapped and unmapped counts, a seeded sample of the last '
+                         'pass\'s alignment records) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='after timing, also run the legs beyond the headline figure: the CPU '
+                         'baseline, the parity legs and the end-to-end (file to file) legs')
     ap.add_argument('--iterations', type=int, default=1,
                     help='cap on remap iterations per step (1: C2; 3 with --pairs 10000000: C3 on '
                          'one GPU); the reference\'s stopping rules still apply')
@@ -1398,6 +1465,13 @@ def main():
                          '(SURVEY.md 8(f)) over the remap.csv of one C2 pass; censor: the '
                          'stage before (FASTQ censor of the C2 reads) plus the FASTQ ingest')
     args = ap.parse_args()
+    if args.parity_full and not args.full:
+        ap.error('--parity-full is one of the --full legs: add --full')
+    if args.dump_outputs and args.stage != 'remap':
+        ap.error('--dump-outputs writes the outputs of the remap stage')
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_parity = args.no_e2e = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return _self_launch(args)
     if args.stage == 'sam2aln':
@@ -1483,6 +1557,8 @@ def main():
     bytes_per_launch = unit_bytes * args.pairs
     avg_s = dom_ms / 1e3 / max(dom_n, 1)
     achieved = bytes_per_launch / avg_s / 1e9 if avg_s > 0 else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, conseqs, new_counts, _unm)
     total_pairs = args.pairs * world * args.steps
     value = (2 if paired else 1) * total_pairs / elapsed
     # DP cell updates (GCUPS next to the roofline): every

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/remap
 mkdir -p $O
 cd $R
-timeout -k 10 400 python3 bench.py --breakdown > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python3 bench.py --full --breakdown > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/prof -o run \
     -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof.err

@@ -27,6 +27,13 @@ def test_single_gpu_stage_refuses_gpus_n():
     assert out.returncode != 0 and 'one GPU' in out.stderr
 
 
+def test_parity_full_needs_full():
+    # the whole-input parity leg is one of the --full legs: asked for without
+    # --full it is refused, never silently left out
+    out = _run(['--parity-full', '1000'])
+    assert out.returncode != 0 and '--full' in out.stderr and '{"metric"' not in out.stdout
+
+
 def test_self_launch_refuses_more_ranks_than_devices():
     # no GPU in the CPU suite's container: zero devices, so --gpus 2 over
     # RCCL is refused before any rank starts

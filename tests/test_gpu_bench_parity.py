@@ -28,7 +28,7 @@ def _bench(args, timeout=500):
 
 @pytest.mark.timeout(600)
 def test_consensus_leg_with_the_filter():
-    d = _bench(['--genomes', 'hiv', '--pairs', '30000', '--steps', '1', '--warmup', '0', '--no-e2e',
+    d = _bench(['--full', '--genomes', 'hiv', '--pairs', '30000', '--steps', '1', '--warmup', '0', '--no-e2e',
                 '--no-cpu-baseline', '--cpu-sample', '30000'])
     p = d['parity']
     assert p['record_mismatches'] == 0
@@ -40,7 +40,7 @@ def test_consensus_leg_with_the_filter():
 
 @pytest.mark.timeout(600)
 def test_parity_full_in_uneven_chunks():
-    d = _bench(['--pairs', '20000', '--steps', '1', '--warmup', '0', '--no-e2e', '--no-cpu-baseline',
+    d = _bench(['--full', '--pairs', '20000', '--steps', '1', '--warmup', '0', '--no-e2e', '--no-cpu-baseline',
                 '--iterations', '2', '--force-iterations', '--parity-full', '7000'])
     w = d['parity']['whole_input']
     assert w['units_checked'] == 20000 and w['chunk_units'] == 7000

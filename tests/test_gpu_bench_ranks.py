@@ -41,7 +41,7 @@ def _bench(args, timeout=400, launcher=True):
 @pytest.mark.timeout(600)
 def test_bench_two_ranks_gloo():
     pairs = 20000
-    d = _bench(['--pairs', str(pairs), '--steps', '1', '--warmup', '1', '--no-cpu-baseline'])
+    d = _bench(['--full', '--pairs', str(pairs), '--steps', '1', '--warmup', '1', '--no-cpu-baseline'])
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak'
     assert d['value'] > 0 and d['ms_per_step'] > 0
     # every read of both ranks' blocks maps to the pol consensus; the tallies
