@@ -218,6 +218,10 @@ int mh_map_stats(mh_ctx *ctx, int64_t *out5);
  * sizes them again. */
 int mh_test_set_capacities(mh_ctx *ctx, int64_t cigar_pool_words, int64_t pileup_events,
                            int64_t pileup_event_bytes, int64_t token_bytes);
+/* Test entry point: on != 0 gives every reference set of later
+ * mh_index_build calls the same cache signature, so only the comparison of
+ * the cached bytes tells two sets apart. */
+int mh_test_force_index_collision(mh_ctx *ctx, int on);
 /* Retries taken so far by those paths: out4[0] CIGAR pool (a mapping pass
  * run again from k_seed), out4[1] pileup events, out4[2] token bytes,
  * out4[3] Gotoh batches run again after a strip's wait timed out. */
@@ -266,20 +270,13 @@ enum { MH_PHASE_INFLATE = 0, MH_PHASE_PARSE = 1, MH_PHASE_UPLOAD = 2, MH_PHASE_F
        MH_PHASE_WRITE = 4, MH_PHASES = 5 };
 int mh_phase_times(mh_ctx *ctx, double *ms, int reset);
 /* The same rows written straight to an open file descriptor at `offset`
- * (pwrite from the formatting threads, no copy through the caller):
- * *written bytes.  The caller moves its file position past them. */
-int mh_write_rows(mh_ctx *ctx, int style, const int64_t *order, int64_t first, int64_t n,
-                  const char *const *refnames, int fd, int64_t offset, int64_t *written);
-/* mh_write_rows that also returns the crc32 of the bytes written (crc NULL:
- * none).  The rows are formatted in chunks on host threads while one
- * thread writes the finished chunks in order. */
+ * (pwrite, no copy through the caller): *written bytes, *crc their crc32
+ * (crc NULL: none).  The rows are formatted in chunks on host threads while
+ * one thread writes the finished chunks in order.  The caller moves its
+ * file position past them. */
 int mh_write_rows_crc(mh_ctx *ctx, int style, const int64_t *order, int64_t first, int64_t n,
                       const char *const *refnames, int fd, int64_t offset, int64_t *written,
                       uint32_t *crc);
-/* (crc32 << 32) | adler32 of a whole open file (zlib's, computed over
- * chunks on host threads) and its size: remap() checks with it that
- * prelim.csv is the file prelim_map() wrote. */
-int mh_file_checksum(int fd, int64_t *size, uint64_t *sum);
 
 /* ---- pileup: replaces sam_to_conseqs' counting (remap.py:141-306) ------ */
 /* External SAM rows (e.g. prelim.csv read back, remap.py:474-498).
@@ -322,10 +319,6 @@ int mh_pileup_dims(mh_ctx *ctx, int *n_refs, int32_t *cap, int64_t *n_events,
                    int64_t *event_bytes);
 int mh_pileup_fetch(mh_ctx *ctx, int32_t *dense, uint8_t *nflag, uint8_t *dflag,
                     int64_t *read_counts, int64_t *first_unit, int32_t *max_pos);
-/* The dense / nflag / dflag rows of one reference (cap positions each):
- * fetching only the references that received pairs keeps a pileup over many
- * seeds from copying every seed's counters. */
-int mh_pileup_fetch_ref(mh_ctx *ctx, int ref, int32_t *dense, uint8_t *nflag, uint8_t *dflag);
 /* The counter rows of n_sel references in one call (one stream
  * synchronisation): dense / nflag / dflag are the whole (n_refs x cap [x 4])
  * arrays, and reference refs[k]'s rows 0 .. max_pos - 1 are written (its

@@ -36,9 +36,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
-#include <functional>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -349,15 +347,6 @@ static void a2c_free_device(A2CState &S)
     S.d_chunks = nullptr;
     S.d_cnt = S.d_first = nullptr;
     S.dcap.clear();
-}
-
-static void a2c_parallel_for(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (auto &x : th) x.join();
 }
 
 // byte classes and the codon table from the caller's translations of the 216
@@ -696,7 +685,7 @@ static int a2c_parse_csv(A2CState &S, const char *text, int64_t len, bool &use_p
         use_pool = true;
         a2c_parse_quoted(parts[0], col, need, S.cls, S.pool);
     } else {
-        a2c_parallel_for(nt, [&](int t) { a2c_parse_part(parts[t], col, need, text, S.cls); });
+        par_for(nt, [&](int t) { a2c_parse_part(parts[t], col, need, text, S.cls); });
     }
     int64_t base = 0;
     for (auto &P : parts) {
@@ -762,11 +751,6 @@ static void a2c_clear_inserts(A2CState &S)
 
 using namespace mh;
 
-static double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 extern "C" int mh_a2c_load_csv(mh_ctx *ctx, int slot, const char *text, int64_t len,
                                const char *codon_chars, int64_t *n_groups)
 {
@@ -783,15 +767,22 @@ extern "C" int mh_a2c_load_csv(mh_ctx *ctx, int slot, const char *text, int64_t 
     auto t0 = std::chrono::steady_clock::now();
     if (int st = a2c_tables(S, codon_chars)) return st;
     bool use_pool = false;
-    if (int st = a2c_parse_csv(S, text ? text : "", len, use_pool)) {
+    int st = 0;
+    try {   // a parser thread's bad_alloc arrives here (par_for)
+        st = a2c_parse_csv(S, text ? text : "", len, use_pool);
+    } catch (const std::exception &e) {
+        set_error("mh_a2c_load_csv: out of memory (%s)", e.what());
+        st = -2;
+    }
+    if (st) {
         S.rows.clear();
         S.g_first.assign(1, 0);
         return st;
     }
     S.t_parse = ms_since(t0);
     auto t1 = std::chrono::steady_clock::now();
-    const int st = use_pool ? a2c_count(c, S, S.pool.data(), (int64_t)S.pool.size())
-                            : a2c_count(c, S, text ? text : "", len);
+    st = use_pool ? a2c_count(c, S, S.pool.data(), (int64_t)S.pool.size())
+                  : a2c_count(c, S, text ? text : "", len);
     if (st) {
         S.rows.clear();
         S.g_first.assign(1, 0);

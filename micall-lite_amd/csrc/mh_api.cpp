@@ -197,6 +197,7 @@ struct CtxEx : Ctx {
     // the reference bytes of each cache entry (every sequence and its NUL, in
     // order): a signature hit is used only when they compare equal
     std::vector<std::string> cache_text;
+    bool force_index_collision = false;   // mh_test_force_index_collision
     std::vector<Rec> rec_cache;
     std::vector<int32_t> csv_rows_info;   // per prelim.csv row: name id, flag, max M run, ref
     std::vector<int32_t> csv_present;     // compact ref id -> index into the @SQ list
@@ -311,9 +312,6 @@ static uint64_t signature(int n, const char *const *seqs, int seedlen)
     }
     return mix64(h, (uint64_t)n);
 }
-
-static void par_for(int nt, const std::function<void(int)> &fn);
-int s2a_threads();   // mh_s2a_host.cpp: host worker count
 
 static int build_index(DevIndex &ix, int n_refs, const char *const *seqs, int seedlen)
 {
@@ -562,37 +560,6 @@ struct Fastq {
     size_t size() const { return len.size(); }
 };
 
-int s2a_threads();   // mh_s2a_host.cpp: host worker count
-
-// fn(0) .. fn(nt-1) on nt threads (the caller's is thread 0).  An
-// exception on any thread (bad_alloc from a text buffer) is kept, every
-// thread is joined, then the first one is rethrown on the caller's thread:
-// none escapes a std::thread (that would terminate the process).
-static void par_for(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::mutex mu;
-    std::exception_ptr first;
-    auto guarded = [&](int t) {
-        try {
-            fn(t);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!first) first = std::current_exception();
-        }
-    };
-    std::vector<std::thread> th;
-    th.reserve((size_t)nt - 1);
-    try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
-    } catch (...) {           // thread creation failed: run the rest here
-        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
-    }
-    guarded(0);
-    for (auto &x : th) x.join();
-    if (first) std::rethrow_exception(first);
-}
-
 // The whole (gzip or plain) file; every concatenated gzip member is decoded
 // (as gzread does), in parallel when there are several (mh_gunzip.cpp).
 static int slurp(const char *path, TextBuf &data)
@@ -612,13 +579,7 @@ static int slurp(const char *path, TextBuf &data)
         raw = (const uint8_t *)map;
     } else if (sz > 0) {
         copy.resize((size_t)sz);
-        int64_t got = 0;
-        while (got < sz) {
-            const ssize_t r = pread(fd, copy.data() + got, (size_t)(sz - got), (off_t)got);
-            if (r <= 0) break;
-            got += r;
-        }
-        if (got != sz) { close(fd); set_error("cannot read FASTQ %s", path); return -3; }
+        if (read_all_at(fd, copy.data(), (size_t)sz, 0)) { close(fd); set_error("cannot read FASTQ %s", path); return -3; }
         raw = (const uint8_t *)copy.data();
     }
     close(fd);
@@ -722,11 +683,6 @@ static int index_fastq(Fastq &fq, const char *path, int64_t *newlines)
     });
     if (too_long >= 0) { set_error("read longer than %d in %s", MAXLEN, path); return -3; }
     return 0;
-}
-
-static double ms_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
 // decode + index one file; the wall time of each half in *dec_ms / *ix_ms
@@ -870,10 +826,9 @@ int mh_index_build(mh_ctx *ctx, int n_refs, const char *const *seqs, int seedlen
     MH_HIP(hipStreamSynchronize(c->stream));
     int64_t total = 0;
     for (int r = 0; r < n_refs; ++r) total += (int64_t)std::strlen(seqs[r]);
-    // MH_INDEX_FORCE_COLLISION=1 (tests): every reference set gets the same
-    // signature, so only the content comparison tells two sets apart
-    const char *force = getenv("MH_INDEX_FORCE_COLLISION");
-    const uint64_t sig = force && *force == '1' ? 0x5eedull : signature(n_refs, seqs, seedlen);
+    // mh_test_force_index_collision (tests): every reference set gets the
+    // same signature, so only the content comparison tells two sets apart
+    const uint64_t sig = c->force_index_collision ? 0x5eedull : signature(n_refs, seqs, seedlen);
     const bool cacheable = total > 65536;
     c->index = DevIndex{};   // cache entries and c->small own their buffers
     for (size_t e = 0; e < c->cache.size(); ++e) {
@@ -1343,6 +1298,13 @@ int mh_map_stats(mh_ctx *ctx, int64_t *out5)
     return 0;
 }
 
+int mh_test_force_index_collision(mh_ctx *ctx, int on)
+{
+    if (!ctx) return -3;
+    X(ctx)->force_index_collision = on != 0;
+    return 0;
+}
+
 int mh_test_set_capacities(mh_ctx *ctx, int64_t cigar_pool_words, int64_t pileup_events,
                            int64_t pileup_event_bytes, int64_t token_bytes)
 {
@@ -1574,99 +1536,140 @@ static void format_row(const CtxEx *c, int style, const Rec &a, int64_t r, const
     used = (size_t)(o - out.data());
 }
 
-// Bytes at file offsets, written by host threads with pwrite.  (Buffered
+// Bytes at file offsets, written by host threads with pwrite (buffered
 // writes to one file serialise on its inode lock; a shared writable mapping
-// filled by every thread instead -- MICALL_WRITE_MMAP=1: the file extended
-// by fallocate, which never shrinks it, so ranks of a sharded job writing
-// their own ranges cannot cut each other's bytes -- measured slower on the
-// GPU box's overlay file system: 0.45 vs 0.24 s for a 1.17 GB prelim.csv.)
-// 0, or an errno.
+// was measured and rejected: DESIGN.md, "Rejected").  0, or an errno.
 struct WritePiece {
     const char *src;
     size_t len;
     int64_t off;
 };
 
-static int write_pieces(int fd, std::vector<WritePiece> pieces)
+static int write_pieces(int fd, const std::vector<WritePiece> &pieces)
 {
-    pieces.erase(std::remove_if(pieces.begin(), pieces.end(),
-                                [](const WritePiece &p) { return p.len == 0; }),
-                 pieces.end());
-    if (pieces.empty()) return 0;
-    int64_t lo = INT64_MAX, hi = 0;
-    for (const WritePiece &p : pieces) {
-        lo = std::min(lo, p.off);
-        hi = std::max(hi, p.off + (int64_t)p.len);
-    }
     // balance: pieces of at most 4 MiB
     std::vector<WritePiece> work;
     for (const WritePiece &p : pieces)
         for (size_t a = 0; a < p.len; a += (size_t)4 << 20)
             work.push_back(WritePiece{p.src + a, std::min(p.len - a, (size_t)4 << 20), p.off + (int64_t)a});
+    if (work.empty()) return 0;
     const int nt = std::max(1, std::min<int>(s2a_threads(), (int)work.size()));
     std::atomic<size_t> next(0);
     std::atomic<int> bad(0);
-    const long pg = sysconf(_SC_PAGESIZE);
-    const int64_t base = lo / pg * pg;
-    void *map = MAP_FAILED;
-    static const bool use_map = getenv("MICALL_WRITE_MMAP") && *getenv("MICALL_WRITE_MMAP") == '1';
-    if (use_map && hi - lo >= ((int64_t)1 << 20) && fallocate(fd, 0, lo, hi - lo) == 0) {
-        // a shared writable mapping needs a descriptor open for reading too:
-        // an output opened 'w' is write-only, so it is opened again read-write
-        // through /proc (the same file; its own offset is not used)
-        char self[64];
-        snprintf(self, sizeof(self), "/proc/self/fd/%d", fd);
-        const int rw = open(self, O_RDWR | O_CLOEXEC);
-        if (rw >= 0) {
-            struct stat a, b;
-            if (fstat(fd, &a) == 0 && fstat(rw, &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino)
-                map = mmap(nullptr, (size_t)(hi - base), PROT_WRITE, MAP_SHARED, rw, (off_t)base);
-            close(rw);
-        }
-    }
-    if (map != MAP_FAILED) {
-        char *m = (char *)map;
-        par_for(nt, [&](int) {
-            for (size_t i; (i = next.fetch_add(1)) < work.size();)
-                std::memcpy(m + (work[i].off - base), work[i].src, work[i].len);
-        });
-        munmap(map, (size_t)(hi - base));
-        return 0;
-    }
     par_for(nt, [&](int) {
-        for (size_t i; (i = next.fetch_add(1)) < work.size();) {
-            const char *src = work[i].src;
-            size_t left = work[i].len;
-            int64_t pos = work[i].off;
-            while (left > 0) {
-                const ssize_t w = pwrite(fd, src, left, (off_t)pos);
-                if (w <= 0) { bad = errno ? errno : EIO; return; }
-                src += w; left -= (size_t)w; pos += w;
-            }
-        }
+        for (size_t i; (i = next.fetch_add(1)) < work.size();)
+            if (const int e = write_all_at(fd, work[i].src, work[i].len, work[i].off)) { bad = e; return; }
     });
     return bad.load();
 }
 
-// The text of rows first .. first+n (or order[first ..]) as one chunk per
-// host thread, in order.  With segment row bounds seg_rows[0 .. n_seg]
-// (relative to `first`, ascending), *seg_at gets the byte offset in the
-// concatenated text at which each bound row starts.
-static int format_chunks_unguarded(CtxEx *c, int style, const int64_t *order, int64_t first,
-                                   int64_t n, const char *const *refnames,
-                                   std::vector<TextBuf> &chunks, int n_seg,
-                                   const int64_t *seg_rows, std::vector<int64_t> *seg_at);
+// What the row formatters share: the fetched records, the validated row
+// selection (rows first .. first+n, or order[first ..]) and the bound on a
+// row's bytes.
+struct RowSource {
+    const CtxEx *c = nullptr;
+    int style = 0;
+    std::vector<Rec> rec;
+    std::vector<uint32_t> pool;
+    const int64_t *order = nullptr;
+    int64_t first = 0, n = 0;
+    const char *const *refnames = nullptr;
+    std::vector<size_t> rn_len;
+    size_t row_max = 0;
+};
 
-// format_chunks_unguarded with an allocation failure on any formatting
-// thread (par_for rethrows it here) reported as -2, not thrown across the ABI
+// 0, or the ABI status (error set)
+static int row_source(CtxEx *c, int style, const int64_t *order, int64_t first, int64_t n,
+                      const char *const *refnames, RowSource &s)
+{
+    s.c = c;
+    s.style = style;
+    s.order = order;
+    s.first = first;
+    s.n = n;
+    s.refnames = refnames;
+    if (order) {
+        if (int st = fetch_recs(c, 0, c->map.n_reads, s.rec, s.pool)) return st;
+        for (int64_t k = 0; k < n; ++k)
+            if (order[first + k] < 0 || order[first + k] >= c->map.n_reads) {
+                set_error("format order index out of range");
+                return -3;
+            }
+    } else if (int st = fetch_recs(c, first, n, s.rec, s.pool)) {
+        return st;
+    }
+    s.rn_len.assign(c->index.n_refs > 0 ? (size_t)c->index.n_refs : 1, 0);
+    size_t name_max = 1, ref_max = 1;
+    for (int k = 0; k < c->index.n_refs; ++k) {
+        s.rn_len[k] = std::strlen(refnames[k]);
+        ref_max = std::max(ref_max, s.rn_len[k]);
+    }
+    for (size_t r = 0; r < c->names.size(); ++r)
+        name_max = std::max(name_max, (size_t)(c->names.off[r + 1] - c->names.off[r]));
+    s.row_max = 2 * name_max + 4 * ref_max + 3 * (size_t)std::max(c->reads.max_len, 1) +
+                12 * MH_MAXOPS + 16 * 12 + 200;
+    return 0;
+}
+
+// (segment bound, byte offset in a chunk)
+typedef std::vector<std::pair<int, size_t>> SegMarks;
+
+// The text of rows k0 .. k1 of s in out.  out is sized for the rows' upper
+// bound up front (not touched until written: no zero fill, no regrowth
+// copies).  With segment row bounds seg_rows[0 .. n_seg], every bound that
+// falls on a row of the range is marked with its byte offset in out.
+static void format_range(const RowSource &s, int64_t k0, int64_t k1, TextBuf &out, std::string &tmp,
+                         int n_seg = 0, const int64_t *seg_rows = nullptr, SegMarks *marks = nullptr)
+{
+    out.resize((size_t)(k1 - k0) * s.row_max + 1);
+    size_t used = 0;
+    int sb = 0;
+    if (seg_rows) {
+        while (sb <= n_seg && seg_rows[sb] < k0) ++sb;
+    }
+    for (int64_t k = k0; k < k1; ++k) {
+        while (seg_rows && sb <= n_seg && seg_rows[sb] == k) marks->emplace_back(sb++, used);
+        const int64_t r = s.order ? s.order[s.first + k] : s.first + k;
+        format_row(s.c, s.style, s.order ? s.rec[r] : s.rec[k], r, s.pool.data(), s.refnames,
+                   s.rn_len.data(), out, used, tmp);
+    }
+    out.resize(used);
+}
+
+// The text of the rows as one chunk per host thread, in order.  With
+// segment row bounds seg_rows[0 .. n_seg] (relative to `first`, ascending),
+// *seg_at gets the byte offset in the concatenated text at which each bound
+// row starts.  An allocation failure on any formatting thread (par_for
+// rethrows it here) is reported as -2, not thrown across the ABI.
 static int format_chunks(CtxEx *c, int style, const int64_t *order, int64_t first, int64_t n,
                          const char *const *refnames, std::vector<TextBuf> &chunks,
                          int n_seg = 0, const int64_t *seg_rows = nullptr,
                          std::vector<int64_t> *seg_at = nullptr)
 {
     try {
-        return format_chunks_unguarded(c, style, order, first, n, refnames, chunks, n_seg, seg_rows,
-                                       seg_at);
+        const auto t0 = std::chrono::steady_clock::now();
+        RowSource src;
+        if (int st = row_source(c, style, order, first, n, refnames, src)) return st;
+        const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 14) + 1));
+        chunks.clear();
+        chunks.resize(nt);
+        std::vector<SegMarks> marks(nt);
+        par_for(nt, [&](int t) {
+            std::string tmp;
+            format_range(src, n * t / nt, n * (t + 1) / nt, chunks[t], tmp, n_seg, seg_rows, &marks[t]);
+        });
+        if (seg_at) {
+            seg_at->assign((size_t)n_seg + 1, -1);
+            int64_t base = 0;
+            for (int t = 0; t < nt; ++t) {
+                for (auto &m : marks[t]) (*seg_at)[m.first] = base + (int64_t)m.second;
+                base += (int64_t)chunks[t].size();
+            }
+            for (int sb = 0; sb <= n_seg; ++sb)   // bounds at the end (row n)
+                if ((*seg_at)[sb] < 0) (*seg_at)[sb] = base;
+        }
+        c->phase_ms[MH_PHASE_FORMAT] += ms_since(t0);
+        return 0;
     } catch (const std::bad_alloc &) {
         chunks.clear();
         set_error("row formatting: out of memory");
@@ -1676,73 +1679,6 @@ static int format_chunks(CtxEx *c, int style, const int64_t *order, int64_t firs
         set_error("row formatting: %s", e.what());
         return -2;
     }
-}
-
-static int format_chunks_unguarded(CtxEx *c, int style, const int64_t *order, int64_t first,
-                                   int64_t n, const char *const *refnames,
-                                   std::vector<TextBuf> &chunks, int n_seg,
-                                   const int64_t *seg_rows, std::vector<int64_t> *seg_at)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<Rec> rec;
-    std::vector<uint32_t> pool;
-    if (order) {
-        if (int st = fetch_recs(c, 0, c->map.n_reads, rec, pool)) return st;
-        for (int64_t k = 0; k < n; ++k)
-            if (order[first + k] < 0 || order[first + k] >= c->map.n_reads) {
-                set_error("format order index out of range");
-                return -3;
-            }
-    } else if (int st = fetch_recs(c, first, n, rec, pool)) {
-        return st;
-    }
-    std::vector<size_t> rn_len(c->index.n_refs > 0 ? (size_t)c->index.n_refs : 1, 0);
-    for (int k = 0; k < c->index.n_refs; ++k) rn_len[k] = std::strlen(refnames[k]);
-    const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 14) + 1));
-    chunks.clear();
-    chunks.resize(nt);
-    // a chunk's bytes are reserved for its rows' upper bound up front (not
-    // touched until written: no zero fill, no regrowth copies)
-    size_t name_max = 1;
-    for (size_t r = 0; r < c->names.size(); ++r)
-        name_max = std::max(name_max, (size_t)(c->names.off[r + 1] - c->names.off[r]));
-    size_t ref_max = 1;
-    for (int k = 0; k < c->index.n_refs; ++k) ref_max = std::max(ref_max, rn_len[k]);
-    const size_t row_max = 2 * name_max + 4 * ref_max + 3 * (size_t)std::max(c->reads.max_len, 1) +
-                           12 * MH_MAXOPS + 16 * 12 + 200;
-    // per thread: (segment bound, byte offset in the thread's chunk)
-    std::vector<std::vector<std::pair<int, size_t>>> marks(nt);
-    par_for(nt, [&](int t) {
-        const int64_t k0 = n * t / nt, k1 = n * (t + 1) / nt;
-        TextBuf &out = chunks[t];
-        out.reserve((size_t)(k1 - k0) * row_max + 1);
-        out.resize((size_t)(k1 - k0) * row_max + 1);
-        size_t used = 0;
-        std::string tmp;
-        int sb = 0;
-        if (seg_rows) {
-            while (sb <= n_seg && seg_rows[sb] < k0) ++sb;
-        }
-        for (int64_t k = k0; k < k1; ++k) {
-            while (seg_rows && sb <= n_seg && seg_rows[sb] == k) marks[t].emplace_back(sb++, used);
-            const int64_t r = order ? order[first + k] : first + k;
-            format_row(c, style, order ? rec[r] : rec[k], r, pool.data(), refnames, rn_len.data(),
-                       out, used, tmp);
-        }
-        out.resize(used);
-    });
-    if (seg_at) {
-        seg_at->assign((size_t)n_seg + 1, -1);
-        int64_t base = 0;
-        for (int t = 0; t < nt; ++t) {
-            for (auto &m : marks[t]) (*seg_at)[m.first] = base + (int64_t)m.second;
-            base += (int64_t)chunks[t].size();
-        }
-        for (int sb = 0; sb <= n_seg; ++sb)   // bounds at the end (row n)
-            if ((*seg_at)[sb] < 0) (*seg_at)[sb] = base;
-    }
-    c->phase_ms[MH_PHASE_FORMAT] += ms_since(t0);
-    return 0;
 }
 
 // Rows formatted and written in one stream: the rows are cut into many
@@ -1756,26 +1692,8 @@ static int format_write_stream(CtxEx *c, int style, const int64_t *order, int64_
                                int64_t *written, uint32_t *crc_out)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<Rec> rec;
-    std::vector<uint32_t> pool;
-    if (order) {
-        if (int st = fetch_recs(c, 0, c->map.n_reads, rec, pool)) return st;
-        for (int64_t k = 0; k < n; ++k)
-            if (order[first + k] < 0 || order[first + k] >= c->map.n_reads) {
-                set_error("format order index out of range");
-                return -3;
-            }
-    } else if (int st = fetch_recs(c, first, n, rec, pool)) {
-        return st;
-    }
-    std::vector<size_t> rn_len(c->index.n_refs > 0 ? (size_t)c->index.n_refs : 1, 0);
-    for (int k = 0; k < c->index.n_refs; ++k) rn_len[k] = std::strlen(refnames[k]);
-    size_t name_max = 1, ref_max = 1;
-    for (size_t r = 0; r < c->names.size(); ++r)
-        name_max = std::max(name_max, (size_t)(c->names.off[r + 1] - c->names.off[r]));
-    for (int k = 0; k < c->index.n_refs; ++k) ref_max = std::max(ref_max, rn_len[k]);
-    const size_t row_max = 2 * name_max + 4 * ref_max + 3 * (size_t)std::max(c->reads.max_len, 1) +
-                           12 * MH_MAXOPS + 16 * 12 + 200;
+    RowSource src;
+    if (int st = row_source(c, style, order, first, n, refnames, src)) return st;
     const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(n / 4096 + 1, 1024));
     std::vector<TextBuf> buf((size_t)nch);
     std::vector<uint32_t> crc((size_t)nch, 0);
@@ -1806,17 +1724,9 @@ static int format_write_stream(CtxEx *c, int style, const int64_t *order, int64_
         try {
             std::string tmp;
             for (int64_t k; (k = next.fetch_add(1)) < nch;) {
-                const int64_t k0 = n * k / nch, k1 = n * (k + 1) / nch;
                 TextBuf &out = buf[(size_t)k];
-                out.resize((size_t)(k1 - k0) * row_max + 1);
-                size_t used = 0;
-                for (int64_t j = k0; j < k1; ++j) {
-                    const int64_t r = order ? order[first + j] : first + j;
-                    format_row(c, style, order ? rec[r] : rec[j], r, pool.data(), refnames, rn_len.data(),
-                               out, used, tmp);
-                }
-                out.resize(used);
-                if (crc_out) crc[(size_t)k] = crc32_update(0, out.data(), used);
+                format_range(src, n * k / nch, n * (k + 1) / nch, out, tmp);
+                if (crc_out) crc[(size_t)k] = crc32_update(0, out.data(), out.size());
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     done[k].store(1);
@@ -1842,15 +1752,10 @@ static int format_write_stream(CtxEx *c, int style, const int64_t *order, int64_
             cv.wait(lk, [&] { return done[k].load() != 0 || failed.load(); });
         }
         if (failed.load()) break;
-        const char *p = buf[(size_t)k].data();
-        size_t left = buf[(size_t)k].size();
-        if (crc_out) total_crc = crc32_join(total_crc, crc[(size_t)k], (int64_t)left);
-        while (left > 0 && !bad) {
-            const ssize_t w = pwrite(fd, p, left, (off_t)pos);
-            if (w <= 0) { bad = errno ? errno : EIO; break; }
-            p += w; left -= (size_t)w; pos += w;
-        }
-        buf[(size_t)k].release();
+        TextBuf &out = buf[(size_t)k];
+        if (crc_out) total_crc = crc32_join(total_crc, crc[(size_t)k], (int64_t)out.size());
+        if (!bad && !(bad = write_all_at(fd, out.data(), out.size(), pos))) pos += (int64_t)out.size();
+        out.release();
     }
     for (auto &t : fmt) t.join();
     if (err) std::rethrow_exception(err);
@@ -1862,12 +1767,6 @@ static int format_write_stream(CtxEx *c, int style, const int64_t *order, int64_
     if (written) *written = pos - offset;
     if (crc_out) *crc_out = total_crc;
     return 0;
-}
-
-int mh_write_rows(mh_ctx *ctx, int style, const int64_t *order, int64_t first, int64_t n,
-                  const char *const *refnames, int fd, int64_t offset, int64_t *written)
-{
-    return mh_write_rows_crc(ctx, style, order, first, n, refnames, fd, offset, written, nullptr);
 }
 
 int mh_write_rows_crc(mh_ctx *ctx, int style, const int64_t *order, int64_t first, int64_t n,
@@ -1991,12 +1890,7 @@ int mh_file_crc32(int fd, int64_t *size, uint32_t *crc)
         std::vector<unsigned char> buf((size_t)CH);
         for (int64_t k; (k = next.fetch_add(1)) < nc;) {
             const int64_t a = k * CH, len = std::min(CH, n - a);
-            int64_t got = 0;
-            while (got < len) {
-                const ssize_t r = pread(fd, buf.data() + got, (size_t)(len - got), (off_t)(a + got));
-                if (r <= 0) { bad = 1; return; }
-                got += r;
-            }
+            if (read_all_at(fd, buf.data(), (size_t)len, a)) { bad = 1; return; }
             part[k] = crc32_update(0, buf.data(), (size_t)len);
         }
     });
@@ -2016,46 +1910,6 @@ int mh_phase_times(mh_ctx *ctx, double *ms, int reset)
         if (ms) ms[k] = c->phase_ms[k];
         if (reset) c->phase_ms[k] = 0.0;
     }
-    return 0;
-}
-
-// crc32 and adler32 of a whole open file (zlib's, combined over chunks read
-// on host threads): (crc32 << 32) | adler32, and its size.
-int mh_file_checksum(int fd, int64_t *size, uint64_t *sum)
-{
-    if (fd < 0 || !sum) return -3;
-    struct stat st;
-    if (fstat(fd, &st) != 0) { set_error("mh_file_checksum: fstat failed"); return -4; }
-    const int64_t n = (int64_t)st.st_size;
-    const int64_t CH = (int64_t)16 << 20;
-    const int64_t nc = (n + CH - 1) / CH;
-    std::vector<uLong> crc((size_t)std::max<int64_t>(nc, 1)), adl((size_t)std::max<int64_t>(nc, 1));
-    std::atomic<int64_t> next(0);
-    std::atomic<int> bad(0);
-    const int nt = std::max(1, std::min<int>(s2a_threads(), (int)std::max<int64_t>(nc, 1)));
-    par_for(nt, [&](int) {
-        std::vector<unsigned char> buf((size_t)CH);
-        for (int64_t k; (k = next.fetch_add(1)) < nc;) {
-            const int64_t a = k * CH, len = std::min(CH, n - a);
-            int64_t got = 0;
-            while (got < len) {
-                const ssize_t r = pread(fd, buf.data() + got, (size_t)(len - got), (off_t)(a + got));
-                if (r <= 0) { bad = 1; return; }
-                got += r;
-            }
-            crc[k] = crc32(crc32(0L, Z_NULL, 0), buf.data(), (uInt)len);
-            adl[k] = adler32(adler32(0L, Z_NULL, 0), buf.data(), (uInt)len);
-        }
-    });
-    if (bad) { set_error("mh_file_checksum: read failed"); return -4; }
-    uLong c0 = crc32(0L, Z_NULL, 0), a0 = adler32(0L, Z_NULL, 0);
-    for (int64_t k = 0; k < nc; ++k) {
-        const int64_t len = std::min(CH, n - k * CH);
-        c0 = crc32_combine(c0, crc[k], (z_off_t)len);
-        a0 = adler32_combine(a0, adl[k], (z_off_t)len);
-    }
-    if (size) *size = n;
-    *sum = ((uint64_t)(c0 & 0xffffffffu) << 32) | (uint64_t)(a0 & 0xffffffffu);
     return 0;
 }
 
@@ -2551,6 +2405,23 @@ extern "C" int mh_reads_fastq_lines(mh_ctx *ctx, int64_t *lines1)
     return 0;
 }
 
+// Layout of the pinned landing area of a pileup's scalars (PileState::land):
+// read_counts and first_unit (int64 per reference), max_pos (int32 per
+// reference), then the four int64 event counters, 8-byte aligned.
+struct Landing {
+    int64_t *read_counts, *first_unit;
+    int32_t *max_pos;
+    int64_t *ev_counters;
+    size_t bytes;
+};
+
+static Landing landing_of(const PileState &P)
+{
+    const size_t nr = (size_t)P.n_refs, ev_at = (20 * nr + 7) & ~(size_t)7;
+    return Landing{(int64_t *)P.land, (int64_t *)(P.land + 8 * nr), (int32_t *)(P.land + 16 * nr),
+                   (int64_t *)(P.land + ev_at), 20 * nr + 64};
+}
+
 int mh_pileup(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int32_t *ref_lens)
 {
     return mh_pileup_only(ctx, source, q_cutoff, n_refs, ref_lens, -1, nullptr);
@@ -2581,7 +2452,7 @@ int mh_pileup_only(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int3
     int st = run_pileup(*c, source, q_cutoff);
     if (st == 0) {
         PileState &P = c->pile;
-        const size_t nr = (size_t)P.n_refs, need = 16 * nr + 4 * nr + 64;
+        const size_t nr = (size_t)P.n_refs, need = landing_of(P).bytes;
         if (P.land_cap < need) {
             if (P.land) hipHostFree(P.land);
             P.land = nullptr;
@@ -2590,12 +2461,12 @@ int mh_pileup_only(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int3
             else P.land = nullptr;
         }
         if (P.land && P.read_counts && P.first_unit && P.max_pos) {
-            bool ok = hipMemcpyAsync(P.land, P.read_counts, 8 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-                      hipMemcpyAsync(P.land + 8 * nr, P.first_unit, 8 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-                      hipMemcpyAsync(P.land + 16 * nr, P.max_pos, 4 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+            const Landing L = landing_of(P);
+            bool ok = hipMemcpyAsync(L.read_counts, P.read_counts, 8 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                      hipMemcpyAsync(L.first_unit, P.first_unit, 8 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                      hipMemcpyAsync(L.max_pos, P.max_pos, 4 * nr, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
             if (ok && P.ev_counters)
-                ok = hipMemcpyAsync(P.land + ((20 * nr + 7) & ~(size_t)7), P.ev_counters, 32,
-                                    hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+                ok = hipMemcpyAsync(L.ev_counters, P.ev_counters, 32, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
             P.land_ok = ok;
         }
         MH_HIP(hipStreamSynchronize(c->stream));
@@ -2616,7 +2487,7 @@ static int aggregate_tokens(CtxEx &c)
     c.tok_count.clear(); c.tok_pool.clear();
     int64_t ctr[4] = {0, 0, 0, 0};
     if (P.ev_counters && P.land_ok)   // landed behind mh_pileup
-        std::memcpy(ctr, P.land + ((20 * (size_t)P.n_refs + 7) & ~(size_t)7), sizeof(ctr));
+        std::memcpy(ctr, landing_of(P).ev_counters, sizeof(ctr));
     else if (P.ev_counters)
         MH_HIP(copy_sync(c, ctr, P.ev_counters, sizeof(ctr), hipMemcpyDeviceToHost));
     const int64_t ne = ctr[0];
@@ -2721,9 +2592,10 @@ int mh_pileup_fetch(mh_ctx *ctx, int32_t *dense, uint8_t *nflag, uint8_t *dflag,
     MH_HIP(hipSetDevice(c->device));
     const size_t cells = (size_t)P.n_refs * P.cap, nr = (size_t)P.n_refs;
     if (!dense && !nflag && !dflag && P.land_ok) {   // the scalars, landed behind mh_pileup
-        if (read_counts) std::memcpy(read_counts, P.land, 8 * nr);
-        if (first_unit) std::memcpy(first_unit, P.land + 8 * nr, 8 * nr);
-        if (max_pos) std::memcpy(max_pos, P.land + 16 * nr, 4 * nr);
+        const Landing L = landing_of(P);
+        if (read_counts) std::memcpy(read_counts, L.read_counts, 8 * nr);
+        if (first_unit) std::memcpy(first_unit, L.first_unit, 8 * nr);
+        if (max_pos) std::memcpy(max_pos, L.max_pos, 4 * nr);
         return 0;
     }
     const FetchPart parts[6] = {{P.dense, sizeof(int32_t) * 4 * cells, dense},
@@ -2733,21 +2605,6 @@ int mh_pileup_fetch(mh_ctx *ctx, int32_t *dense, uint8_t *nflag, uint8_t *dflag,
                                 {P.first_unit, sizeof(int64_t) * nr, first_unit},
                                 {P.max_pos, sizeof(int32_t) * nr, max_pos}};
     return fetch_parts(*c, parts, 6);
-}
-
-int mh_pileup_fetch_ref(mh_ctx *ctx, int ref, int32_t *dense, uint8_t *nflag, uint8_t *dflag)
-{
-    if (!ctx) return -3;
-    CtxEx *c = X(ctx);
-    PileState &P = c->pile;
-    if (!P.dense) { set_error("no pileup (call mh_pileup)"); return -3; }
-    if (ref < 0 || ref >= P.n_refs) { set_error("mh_pileup_fetch_ref: ref %d out of range", ref); return -3; }
-    MH_HIP(hipSetDevice(c->device));
-    const int64_t base = (int64_t)ref * P.cap;
-    const FetchPart parts[3] = {{P.dense + 4 * base, sizeof(int32_t) * 4 * (size_t)P.cap, dense},
-                                {P.nflag + base, (size_t)P.cap, nflag},
-                                {P.dflag + base, (size_t)P.cap, dflag}};
-    return fetch_parts(*c, parts, 3);
 }
 
 int mh_pileup_fetch_refs(mh_ctx *ctx, int n_sel, const int32_t *refs, int32_t *dense, uint8_t *nflag,
@@ -2761,7 +2618,7 @@ int mh_pileup_fetch_refs(mh_ctx *ctx, int n_sel, const int32_t *refs, int32_t *d
     // each reference's last counted position (landed behind mh_pileup, else fetched)
     std::vector<int32_t> mx((size_t)std::max(P.n_refs, 1));
     if (P.land_ok && P.land)
-        std::memcpy(mx.data(), P.land + 16 * (size_t)P.n_refs, sizeof(int32_t) * (size_t)P.n_refs);
+        std::memcpy(mx.data(), landing_of(P).max_pos, sizeof(int32_t) * (size_t)P.n_refs);
     else
         MH_HIP(copy_sync(*c, mx.data(), P.max_pos, sizeof(int32_t) * (size_t)P.n_refs, hipMemcpyDeviceToHost));
     std::vector<FetchPart> parts;
@@ -2796,6 +2653,14 @@ int mh_pileup_events(mh_ctx *ctx, int32_t *ref, int32_t *pos, int32_t *tok_off, 
     return 0;
 }
 
+// an exception from a host thread of the Gotoh batch (bad_alloc; par_for
+// rethrows it on the caller) as the ABI's -2
+static int gotoh_threw(const char *entry, const std::exception &e)
+{
+    set_error("%s: out of memory (%s)", entry, e.what());
+    return -2;
+}
+
 int mh_gotoh_align(mh_ctx *ctx, const char *seq1, const char *seq2, int gop, int gep,
                    int is_global, const char *alphabet, const int *matrix, char *out1, char *out2,
                    int cap, int *score)
@@ -2803,7 +2668,11 @@ int mh_gotoh_align(mh_ctx *ctx, const char *seq1, const char *seq2, int gop, int
     if (!ctx || !seq1 || !seq2 || !alphabet || !matrix || !out1 || !out2 || !score) return -3;
     CtxEx *c = X(ctx);
     MH_HIP(hipSetDevice(c->device));
-    return run_gotoh(*c, seq1, seq2, gop, gep, is_global, alphabet, matrix, out1, out2, cap, score);
+    try {
+        return run_gotoh(*c, seq1, seq2, gop, gep, is_global, alphabet, matrix, out1, out2, cap, score);
+    } catch (const std::exception &e) {
+        return gotoh_threw("mh_gotoh_align", e);
+    }
 }
 
 int mh_gotoh_align_batch(mh_ctx *ctx, int count, const char *const *seq1,
@@ -2816,8 +2685,12 @@ int mh_gotoh_align_batch(mh_ctx *ctx, int count, const char *const *seq1,
         return -3;
     CtxEx *c = X(ctx);
     MH_HIP(hipSetDevice(c->device));
-    return run_gotoh_batch(*c, count, seq1, seq2, gop, gep, is_global, alphabet, matrix, out1,
-                           out2, cap, score, status);
+    try {
+        return run_gotoh_batch(*c, count, seq1, seq2, gop, gep, is_global, alphabet, matrix, out1,
+                               out2, cap, score, status);
+    } catch (const std::exception &e) {
+        return gotoh_threw("mh_gotoh_align_batch", e);
+    }
 }
 
 int mh_gotoh_distance_batch(mh_ctx *ctx, int count, const char *const *seq1, const char *const *seq2,
@@ -2829,8 +2702,12 @@ int mh_gotoh_distance_batch(mh_ctx *ctx, int count, const char *const *seq1, con
         return -3;
     CtxEx *c = X(ctx);
     MH_HIP(hipSetDevice(c->device));
-    return run_gotoh_distance_batch(*c, count, seq1, seq2, text, gop, gep, is_global, alphabet, matrix,
-                                    dist, score, status);
+    try {
+        return run_gotoh_distance_batch(*c, count, seq1, seq2, text, gop, gep, is_global, alphabet,
+                                        matrix, dist, score, status);
+    } catch (const std::exception &e) {
+        return gotoh_threw("mh_gotoh_distance_batch", e);
+    }
 }
 
 int mh_top_tokens(int32_t length, int32_t rows, const int32_t *dense, const uint8_t *nflag,
@@ -3031,16 +2908,18 @@ int mh_levenshtein_batch(int count, const char *const *a, const char *const *b, 
         cost[(size_t)t] = (double)std::strlen(a[t]) * (double)std::strlen(b[t]);
     }
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost[(size_t)x] > cost[(size_t)y]; });
-    std::vector<std::thread> pool;
     std::atomic<int> next(0);
-    for (int w = 0; w < threads; ++w)
-        pool.emplace_back([&]() {
+    try {
+        par_for(threads, [&](int) {
             for (int i = next++; i < count; i = next++) {
                 const int t = order[(size_t)i];
                 out[t] = mh_levenshtein(a[t], b[t]);
             }
         });
-    for (auto &th : pool) th.join();
+    } catch (const std::exception &e) {
+        set_error("mh_levenshtein_batch: out of memory (%s)", e.what());
+        return -2;
+    }
     return 0;
 }
 

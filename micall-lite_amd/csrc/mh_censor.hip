@@ -29,12 +29,9 @@
 #include <chrono>
 #include <cstring>
 #include <exception>
-#include <functional>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <string_view>
-#include <system_error>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -44,8 +41,6 @@
 #include "mh_internal.h"
 
 namespace mh {
-
-int s2a_threads();   // mh_s2a_host.cpp: host worker count
 
 struct CensorState {
     TextBuf text;                           // the FASTQ (censored in place)
@@ -82,42 +77,11 @@ static void censor_free_device(CensorState &C)
     C.cap_text = C.cap_rec = C.cap_bad = 0;
 }
 
-// fn(t) on nt threads; the first exception a worker throws (an allocation
-// failure) is rethrown here once every worker has ended
-static void cz_parallel(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::exception_ptr err;
-    std::mutex mu;
-    auto guarded = [&](int t) {
-        try {
-            fn(t);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!err) err = std::current_exception();
-        }
-    };
-    std::vector<std::thread> th;
-    try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
-    } catch (const std::system_error &) {   // no more threads: the rest run here
-        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
-    }
-    guarded(0);
-    for (auto &x : th) x.join();
-    if (err) std::rethrow_exception(err);
-}
-
 void censor_free(Ctx &c)
 {
     if (c.censor) censor_free_device(*c.censor);
     delete c.censor;
     c.censor = nullptr;
-}
-
-static double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // ---------------------------------------------------------------------------
@@ -208,7 +172,7 @@ static int split_records(CensorState &C, const TileMap &tiles)
     // after every newline that is not the text's last byte
     std::vector<int64_t> cnt((size_t)nt + 1, 0);
     auto chunk = [&](int t, int64_t &a, int64_t &b) { a = n * t / nt; b = n * (t + 1) / nt; };
-    cz_parallel(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         int64_t a, b, k = 0;
         chunk(t, a, b);
         for (const char *p = T + a, *e = T + b; p < e;) {
@@ -227,7 +191,7 @@ static int split_records(CensorState &C, const TileMap &tiles)
     }
     std::unique_ptr<int64_t[]> starts(new int64_t[(size_t)std::max<int64_t>(nl, 1)]);
     if (nl) starts[0] = 0;
-    cz_parallel(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         int64_t a, b, k = 1 + cnt[(size_t)t];
         chunk(t, a, b);
         for (const char *p = T + a, *e = T + b; p < e;) {
@@ -249,7 +213,7 @@ static int split_records(CensorState &C, const TileMap &tiles)
         while (e > a && py_space((unsigned char)T[e - 1])) --e;
         return (int32_t)(e - a);
     };
-    cz_parallel(rt, [&](int t) {
+    par_for(rt, [&](int t) {
         for (int64_t r = nr * t / rt; r < nr * (t + 1) / rt; ++r) {
             const int64_t k = 4 * r;
             const int64_t ha = starts[(size_t)k], he = starts[(size_t)k + 1];
@@ -393,12 +357,11 @@ static int censor_emit(CensorState &C, int dst_gzip)
             if (gzip_member("", 0, C.out, 1)) { set_error("censor: deflate failed"); return -2; }
         }
         if (C.sink_fd >= 0 && C.out.size()) {
-            const ssize_t w = pwrite(C.sink_fd, C.out.data(), C.out.size(), (off_t)C.sink_pos);
-            if (w != (ssize_t)C.out.size()) {
-                set_error("censor: write failed (%s)", strerror(errno ? errno : EIO));
+            if (const int e = write_all_at(C.sink_fd, C.out.data(), C.out.size(), C.sink_pos)) {
+                set_error("censor: write failed (%s)", strerror(e));
                 return -4;
             }
-            C.sink_pos += w;
+            C.sink_pos += (int64_t)C.out.size();
             C.out.clear();
         }
         return 0;
@@ -417,17 +380,13 @@ static int censor_emit(CensorState &C, int dst_gzip)
         for (int64_t b = 0; b < nb; ++b) {
             while (!done[b].load(std::memory_order_acquire) && !dead) std::this_thread::yield();
             if (dead || err) return;
-            const char *p = part[(size_t)b].data();
-            size_t left = part[(size_t)b].size();
-            while (left > 0) {
-                const ssize_t w = pwrite(C.sink_fd, p, left, (off_t)C.sink_pos);
-                if (w <= 0) { C.sink_err = errno ? errno : EIO; dead = 1; return; }
-                p += w; left -= (size_t)w; C.sink_pos += w;
-            }
-            part[(size_t)b].release();
+            TextBuf &blk = part[(size_t)b];
+            if ((C.sink_err = write_all_at(C.sink_fd, blk.data(), blk.size(), C.sink_pos))) { dead = 1; return; }
+            C.sink_pos += (int64_t)blk.size();
+            blk.release();
         }
     };
-    cz_parallel(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         if (stream && t == 0) { write_blocks(); return; }
         TextBuf raw;
         struct Dead {   // a throw out of a block maker releases the writer
@@ -466,7 +425,7 @@ static int censor_emit(CensorState &C, int dst_gzip)
     for (int64_t b = 0; b < nb; ++b) off[(size_t)b + 1] = off[(size_t)b] + part[(size_t)b].size();
     C.out.resize(off[(size_t)nb]);
     next = 0;
-    cz_parallel(nt, [&](int) {
+    par_for(nt, [&](int) {
         for (int64_t b; (b = next.fetch_add(1)) < nb;) {
             memcpy(C.out.data() + off[(size_t)b], part[(size_t)b].data(), part[(size_t)b].size());
             part[(size_t)b].release();
@@ -621,18 +580,11 @@ extern "C" int mh_censor_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *wri
     Ctx &c = *ctx_of(ctx);
     if (!c.censor) { set_error("mh_censor_write: no censor results"); return -3; }
     CensorState &C = *c.censor;
-    const char *p = C.out.data();
-    size_t left = C.out.size();
-    int64_t pos = offset;
-    while (left > 0) {
-        const ssize_t w = pwrite(fd, p, left, (off_t)pos);
-        if (w <= 0) {
-            set_error("mh_censor_write: write failed (%s)", strerror(errno ? errno : EIO));
-            return -4;
-        }
-        p += w; left -= (size_t)w; pos += w;
+    if (const int e = write_all_at(fd, C.out.data(), C.out.size(), offset)) {
+        set_error("mh_censor_write: write failed (%s)", strerror(e));
+        return -4;
     }
-    if (written) *written = pos - offset;
+    if (written) *written = (int64_t)C.out.size();
     C.out.release();
     return 0;
 }

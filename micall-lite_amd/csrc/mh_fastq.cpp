@@ -36,15 +36,11 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <exception>
-#include <functional>
 #include <memory>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 
 #include "mh_fastq.h"
@@ -53,7 +49,6 @@
 
 namespace mh {
 void set_error(const char *fmt, ...);
-int s2a_threads();
 }
 
 using namespace mh;
@@ -93,11 +88,9 @@ int view_file(const char *path, int fd_in, FileView &v)
     }
     if (!v.p && v.size > 0) {
         v.copy.resize((size_t)v.size);
-        int64_t got = 0;
-        while (got < v.size) {
-            const ssize_t r = pread(fd, v.copy.data() + got, (size_t)(v.size - got), (off_t)got);
-            if (r <= 0) { set_error("cannot read FASTQ %s", path ? path : "(descriptor)"); rc = -3; break; }
-            got += r;
+        if (read_all_at(fd, v.copy.data(), (size_t)v.size, 0)) {
+            set_error("cannot read FASTQ %s", path ? path : "(descriptor)");
+            rc = -3;
         }
         v.p = (const uint8_t *)v.copy.data();
     }
@@ -143,11 +136,6 @@ int64_t cut_at(const FileView &v, int64_t x)
     return x - before <= after - x ? before : after;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
-
 }  // namespace
 
 struct mh_fastq {
@@ -171,8 +159,7 @@ void text_info(const TextBuf &d, int64_t *info)
     const int64_t n = (int64_t)d.size();
     const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 22) + 1));
     std::vector<int64_t> cnt(nt, 0);
-    std::vector<std::thread> th;
-    auto count = [&](int t) {
+    par_for(nt, [&](int t) {
         const char *a = d.data() + n * t / nt, *b = d.data() + n * (t + 1) / nt;
         int64_t k = 0;
         while (a < b) {
@@ -182,14 +169,7 @@ void text_info(const TextBuf &d, int64_t *info)
             a = q + 1;
         }
         cnt[t] = k;
-    };
-    try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(count, t);
-    } catch (const std::system_error &) {   // no more threads: the rest run here
-        for (int t = (int)th.size() + 1; t < nt; ++t) count(t);
-    }
-    count(0);
-    for (auto &x : th) x.join();
+    });
     int64_t nl = 0;
     for (int64_t k : cnt) nl += k;
     info[3] = n;

@@ -44,7 +44,6 @@
 #include <functional>
 #include <memory>
 #include <thread>
-#include <system_error>
 #include <algorithm>
 #include <mutex>
 #include <type_traits>
@@ -1028,15 +1027,7 @@ static void gotoh_par(int count, const std::function<void(int)> &fn)
 {
     const int nt = std::max(1, std::min({count, 16, (int)std::thread::hardware_concurrency()}));
     std::atomic<int> next(0);
-    auto run = [&]() { for (int t; (t = next.fetch_add(1)) < count;) fn(t); };
-    std::vector<std::thread> th;
-    try {
-        for (int k = 1; k < nt; ++k) th.emplace_back(run);
-    } catch (const std::system_error &) {
-        // fewer threads: the ones started and this one share the work
-    }
-    run();
-    for (auto &x : th) x.join();
+    par_for(nt, [&](int) { for (int t; (t = next.fetch_add(1)) < count;) fn(t); });
 }
 
 // the zeroed work block (without the tie planes, which k_gotoh_fwd writes

@@ -7,6 +7,7 @@
 #include <sys/mman.h>
 #include <cerrno>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -189,15 +190,6 @@ bool member_header(const uint8_t *p, int64_t avail)
 
 uint32_t le32(const uint8_t *p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
 
-void run_threads(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (auto &x : th) x.join();
-}
-
 // Concatenated members decoded in parallel.  Every header-shaped offset is a
 // candidate member start; the member ending at the next candidate has its
 // size (ISIZE) in the 4 bytes before it.  Each candidate span is decoded
@@ -212,7 +204,7 @@ int gunzip_members(const LdApi &api, const uint8_t *src, int64_t len, Buf &out, 
     {
         const int nt = threads;
         std::vector<std::vector<int64_t>> part(nt);
-        run_threads(nt, [&](int t) {
+        par_for(nt, [&](int t) {
             const int64_t a = len * t / nt, b = len * (t + 1) / nt;
             const uint8_t *p = src + a;
             while (p < src + b) {
@@ -234,7 +226,7 @@ int gunzip_members(const LdApi &api, const uint8_t *src, int64_t len, Buf &out, 
         // by the caller.
         std::vector<char> keep(cand.size(), 1);
         std::atomic<size_t> next(1);
-        run_threads(std::min<int>(threads, (int)cand.size()), [&](int) {
+        par_for(std::min<int>(threads, (int)cand.size()), [&](int) {
             for (size_t j; (j = next.fetch_add(1)) < cand.size();)
                 keep[j] = gzip_member_probe(src + cand[j], len - cand[j], 16384);
         });
@@ -266,7 +258,7 @@ int gunzip_members(const LdApi &api, const uint8_t *src, int64_t len, Buf &out, 
         out.resize(at[k]);
         std::vector<char> ok(k, 0);
         std::atomic<size_t> next(0);
-        run_threads(std::min<int>(threads, (int)k), [&](int) {
+        par_for(std::min<int>(threads, (int)k), [&](int) {
             for (size_t j; (j = next.fetch_add(1)) < k;)
                 ok[j] = plausible[j] &&
                         member_exact(api, src + beg[j], end[j] - beg[j], &out[at[j]],
@@ -291,6 +283,56 @@ int gunzip_members(const LdApi &api, const uint8_t *src, int64_t len, Buf &out, 
 }
 
 }  // namespace
+
+void par_for(int nt, const std::function<void(int)> &fn)
+{
+    if (nt <= 1) { fn(0); return; }
+    std::mutex mu;
+    std::exception_ptr first;
+    auto guarded = [&](int t) {
+        try {
+            fn(t);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!first) first = std::current_exception();
+        }
+    };
+    std::vector<std::thread> th;
+    th.reserve((size_t)nt - 1);
+    try {
+        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
+    } catch (...) {           // thread creation failed: run the rest here
+        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
+    }
+    guarded(0);
+    for (auto &x : th) x.join();
+    if (first) std::rethrow_exception(first);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+int write_all_at(int fd, const void *p, size_t n, int64_t off)
+{
+    for (size_t done = 0; done < n;) {
+        const ssize_t w = pwrite(fd, (const char *)p + done, n - done, (off_t)(off + (int64_t)done));
+        if (w <= 0) return w < 0 ? errno : EIO;
+        done += (size_t)w;
+    }
+    return 0;
+}
+
+int read_all_at(int fd, void *p, size_t n, int64_t off)
+{
+    for (size_t done = 0; done < n;) {
+        const ssize_t r = pread(fd, (char *)p + done, n - done, (off_t)(off + (int64_t)done));
+        if (r <= 0) return r < 0 ? errno : EIO;
+        done += (size_t)r;
+    }
+    return 0;
+}
 
 void *ld_raw_alloc()
 {
@@ -356,13 +398,20 @@ int map_text_file(int fd, const char **text, size_t *len)
     if (m == MAP_FAILED) { set_error("map_text_file: mmap failed (%s)", strerror(errno)); return -3; }
     const char *t = (const char *)m;
     const int nt = std::max(1, std::min<int>(gunzip_threads(), (int)(n >> 20) + 1));
-    std::vector<char> cr((size_t)nt, 0);
-    run_threads(nt, [&](int k) {
-        const size_t a = n * (size_t)k / (size_t)nt, b = n * (size_t)(k + 1) / (size_t)nt;
-        cr[(size_t)k] = memchr(t + a, '\r', b - a) != nullptr;
-    });
-    for (char c : cr)
-        if (c) { munmap(m, n); return 1; }
+    bool any_cr = false;
+    try {
+        std::vector<char> cr((size_t)nt, 0);
+        par_for(nt, [&](int k) {
+            const size_t a = n * (size_t)k / (size_t)nt, b = n * (size_t)(k + 1) / (size_t)nt;
+            cr[(size_t)k] = memchr(t + a, '\r', b - a) != nullptr;
+        });
+        for (char c : cr) any_cr |= c != 0;
+    } catch (const std::exception &e) {   // no memory for the fan-out itself
+        munmap(m, n);
+        set_error("map_text_file: out of memory (%s)", e.what());
+        return -2;
+    }
+    if (any_cr) { munmap(m, n); return 1; }
     *text = t;
     *len = n;
     return 0;

@@ -1,14 +1,34 @@
-// mh_gunzip.h -- whole-buffer gunzip (mh_gunzip.cpp).
+// mh_gunzip.h -- host utilities shared by every translation unit (thread
+// fan-out, whole-buffer file I/O, large buffers, crc32) and the whole-buffer
+// gunzip; all defined in mh_gunzip.cpp unless noted.
 #pragma once
 #include <stdint.h>
 
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 
 namespace mh {
+
+// fn(0) .. fn(nt-1) on nt threads (the caller's is thread 0; nt <= 1 runs
+// fn(0) inline).  An exception on any thread (bad_alloc from a text buffer)
+// is kept, every thread is joined, then the first one is rethrown on the
+// caller's thread: none escapes a std::thread (that would terminate the
+// process).  When a thread cannot be created the remaining indices run on
+// the caller.
+void par_for(int nt, const std::function<void(int)> &fn);
+// host worker count: min(16, hardware threads, OMP_NUM_THREADS) (mh_s2a_host.cpp)
+int s2a_threads();
+// milliseconds since t
+double ms_since(std::chrono::steady_clock::time_point t);
+// All n bytes at p written to / read from fd at offset off: 0, or an errno
+// (a transfer that stops short, or moves nothing, counts as EIO).
+int write_all_at(int fd, const void *p, size_t n, int64_t off);
+int read_all_at(int fd, void *p, size_t n, int64_t off);
 
 // Large host buffers: anonymous mappings with transparent huge pages asked
 // for (the box's THP mode is "madvise"), so filling and freeing a GB-sized

@@ -40,7 +40,6 @@
 #include <cstring>
 #include <functional>
 #include <memory>
-#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -219,27 +218,12 @@ int inflate_to(const uint8_t *p, int64_t nbytes, int64_t bit, const uint8_t *dic
 // back to the serial inflate instead of the process terminating
 bool threads_run(int nt, const std::function<void(int)> &fn)
 {
-    std::atomic<int> failed(0);
-    auto guarded = [&](int t) {
-        try {
-            fn(t);
-        } catch (...) {
-            failed = 1;
-        }
-    };
-    if (nt <= 1) {
-        guarded(0);
-        return !failed;
-    }
-    std::vector<std::thread> th;
     try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
-    } catch (const std::system_error &) {   // no more threads: the rest run here
-        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
+        par_for(nt, fn);
+        return true;
+    } catch (...) {
+        return false;
     }
-    guarded(0);
-    for (auto &x : th) x.join();
-    return !failed;
 }
 
 // The DEFLATE bits [b0, b1) of src, byte-aligned, into in[pre ..) (the

@@ -17,11 +17,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <functional>
-#include <mutex>
 #include <string>
-#include <system_error>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -42,32 +39,6 @@ int s2a_threads()
     }
     if (n < 1) n = 1;
     return n > 16 ? 16 : n;
-}
-
-// fn(t) on nt threads; the first exception a worker throws (an allocation
-// failure) is rethrown here once every worker has ended
-static void parallel_for(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::exception_ptr err;
-    std::mutex mu;
-    auto guarded = [&](int t) {
-        try {
-            fn(t);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!err) err = std::current_exception();
-        }
-    };
-    std::vector<std::thread> th;
-    try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
-    } catch (const std::system_error &) {   // no more threads: the rest run here
-        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
-    }
-    guarded(0);
-    for (auto &x : th) x.join();
-    if (err) std::rethrow_exception(err);
 }
 
 struct FieldRef {
@@ -339,7 +310,7 @@ int s2a_parse(S2AState &S, const char *text, int64_t len, int64_t body_lo, int64
         if (cut[t] < cut[t - 1]) cut[t] = cut[t - 1];
     }
     std::vector<int64_t> quotes(nt, 0);
-    parallel_for(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         int64_t n = 0;
         for (const char *c = cut[t]; c < cut[t + 1]; ++c) n += *c == '"';
         quotes[t] = n;
@@ -352,7 +323,7 @@ int s2a_parse(S2AState &S, const char *text, int64_t len, int64_t body_lo, int64
     std::vector<Part> parts(nt);
     for (int t = 0; t < nt; ++t) { parts[t].beg = cut[t]; parts[t].end = cut[t + 1]; }
     s2a_mark(tp, "split");
-    parallel_for(nt, [&](int t) { parse_part(parts[t], col); });
+    par_for(nt, [&](int t) { parse_part(parts[t], col); });
     s2a_mark(tp, "parts");
     int64_t base = 0;
     for (auto &P : parts) {
@@ -390,7 +361,7 @@ int s2a_parse(S2AState &S, const char *text, int64_t len, int64_t body_lo, int64
     S.qshort.resize(nr); S.soff.resize(nr); S.slen.resize(nr); S.cig_off.resize(nr);
     S.n_cig.resize(nr); S.cig.resize((size_t)g0[nt]);
     std::vector<uint64_t> qhash(nr);
-    parallel_for(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         const Part &P = parts[t];
         const int64_t b = r0[t];
         memcpy(&S.qpool[q0[t]], P.qpool.data(), P.qpool.size());
@@ -504,11 +475,11 @@ static void parallel_sort(std::vector<int64_t> &v, Cmp cmp, int nt)
     if (nt <= 1 || n < 65536) { std::sort(v.begin(), v.end(), cmp); return; }
     std::vector<size_t> b(nt + 1);
     for (int t = 0; t <= nt; ++t) b[t] = n * (size_t)t / (size_t)nt;
-    parallel_for(nt, [&](int t) { std::sort(v.begin() + b[t], v.begin() + b[t + 1], cmp); });
+    par_for(nt, [&](int t) { std::sort(v.begin() + b[t], v.begin() + b[t + 1], cmp); });
     for (int w = 1; w < nt; w *= 2) {
         std::vector<std::pair<int, int>> jobs;
         for (int t = 0; t + w < nt; t += 2 * w) jobs.push_back({t, std::min(t + 2 * w, nt)});
-        parallel_for((int)jobs.size(), [&](int j) {
+        par_for((int)jobs.size(), [&](int j) {
             const int a = jobs[j].first, m = a + w, z = jobs[j].second;
             std::inplace_merge(v.begin() + b[a], v.begin() + b[m], v.begin() + b[z], cmp);
         });
@@ -531,15 +502,7 @@ struct TextSink {
             if (!s.empty()) out->push_back(std::move(s));
             return;
         }
-        const char *p = s.data();
-        size_t left = s.size();
-        while (left > 0 && !err) {
-            const ssize_t w = pwrite(fd, p, left, (off_t)pos);
-            if (w <= 0) { err = errno ? errno : EIO; break; }
-            p += (size_t)w;
-            left -= (size_t)w;
-            pos += w;
-        }
+        if (!err && !(err = write_all_at(fd, s.data(), s.size(), pos))) pos += (int64_t)s.size();
         std::string().swap(s);
     }
 };
@@ -555,7 +518,7 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
     if (n < 4096) nt = 1;
     if (sink.out) {
         std::vector<std::string> piece(nt);
-        parallel_for(nt, [&](int t) { fn(piece[t], n * t / nt, n * (t + 1) / nt); });
+        par_for(nt, [&](int t) { fn(piece[t], n * t / nt, n * (t + 1) / nt); });
         for (auto &x : piece) sink.put(x);
         return;
     }
@@ -571,30 +534,28 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
     for (int64_t j = 0; j < nj; ++j) done[j].store(0);
     std::atomic<int64_t> next(0);
     std::atomic<int> failed(0);
-    std::exception_ptr exc;
-    std::mutex mu;
-    auto work = [&]() {
-        try {
-            for (int64_t j; !failed && (j = next.fetch_add(1)) < nj;) {
-                fn(buf[(size_t)j], j * STREAM_ROWS, std::min(n, (j + 1) * STREAM_ROWS));
-                done[j].store(1, std::memory_order_release);
+    // thread 0 (the caller) writes; threads 1 .. format.  Should a thread not
+    // start, its formatting runs here before the writing (par_for).
+    par_for(std::max(1, nt - 1) + 1, [&](int t) {
+        if (t) {
+            try {
+                for (int64_t j; !failed && (j = next.fetch_add(1)) < nj;) {
+                    fn(buf[(size_t)j], j * STREAM_ROWS, std::min(n, (j + 1) * STREAM_ROWS));
+                    done[j].store(1, std::memory_order_release);
+                }
+            } catch (...) {
+                failed = 1;   // the writer stops waiting; par_for rethrows
+                throw;
             }
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!exc) exc = std::current_exception();
-            failed = 1;
+            return;
         }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < std::max(1, nt - 1); ++t) th.emplace_back(work);
-    for (int64_t j = 0; j < nj && !failed && !sink.err; ++j) {
-        while (!done[j].load(std::memory_order_acquire) && !failed) std::this_thread::yield();
-        if (failed) break;
-        sink.put(buf[(size_t)j]);
-    }
-    failed = 1;   // a write error: the formatters stop at their next job
-    for (auto &x : th) x.join();
-    if (exc) std::rethrow_exception(exc);
+        for (int64_t j = 0; j < nj && !failed && !sink.err; ++j) {
+            while (!done[j].load(std::memory_order_acquire) && !failed) std::this_thread::yield();
+            if (failed) break;
+            sink.put(buf[(size_t)j]);
+        }
+        failed = 1;   // a write error: the formatters stop at their next job
+    });
 }
 
 // aligned.csv (sam2aln.py:459-478): per rname in first-seen order, the
@@ -629,7 +590,7 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
     // cheap to compare -- then each run of equal keys by its sequence, the
     // runs sorted in parallel (no serial merge of memcmp comparisons)
     std::vector<uint64_t> key((size_t)S.n_unique);
-    parallel_for(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         for (int64_t k = S.n_unique * t / nt; k < S.n_unique * (t + 1) / nt; ++k)
             key[(size_t)k] = (uint64_t)(uint32_t)S.uniq[2 * k + 1] << 32 |
                              (uint32_t)(S.res[4 * S.uniq[2 * k] + 1] ^ (int32_t)0x80000000);
@@ -644,7 +605,7 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
             if (key[(size_t)v[i]] != key[(size_t)v[i - 1]]) runs.push_back(i);
         runs.push_back(v.size());
         std::atomic<size_t> next_run(0);
-        parallel_for(nt, [&](int) {
+        par_for(nt, [&](int) {
             for (size_t j; (j = next_run.fetch_add(1)) + 1 < runs.size();)
                 if (runs[j + 1] - runs[j] > 1) std::sort(v.begin() + runs[j], v.begin() + runs[j + 1], cmp);
         });

@@ -33,14 +33,9 @@
 
 #include <algorithm>
 #include <chrono>
-#include <atomic>
 #include <cstring>
 #include <exception>
-#include <functional>
-#include <mutex>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 
 #include "mh_sam2aln.h"
@@ -114,30 +109,6 @@ uint64_t seq_hash(int32_t gname, int32_t offset, const char *p, int32_t n)
     return mix64(h ^ w ^ 0x5bd1e995ull);
 }
 
-void run_threads(int nt, const std::function<void(int)> &fn)
-{
-    if (nt <= 1) { fn(0); return; }
-    std::exception_ptr err;
-    std::mutex mu;
-    auto guarded = [&](int t) {
-        try {
-            fn(t);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!err) err = std::current_exception();
-        }
-    };
-    std::vector<std::thread> th;
-    try {
-        for (int t = 1; t < nt; ++t) th.emplace_back(guarded, t);
-    } catch (const std::system_error &) {   // no more threads: the rest run here
-        for (int t = (int)th.size() + 1; t < nt; ++t) guarded(t);
-    }
-    guarded(0);
-    for (auto &x : th) x.join();
-    if (err) std::rethrow_exception(err);
-}
-
 template <class Cmp>
 void par_sort(std::vector<const S2ARec *> &v, Cmp cmp)
 {
@@ -146,11 +117,11 @@ void par_sort(std::vector<const S2ARec *> &v, Cmp cmp)
     if (nt <= 1 || n < 65536) { std::sort(v.begin(), v.end(), cmp); return; }
     std::vector<size_t> b((size_t)nt + 1);
     for (int t = 0; t <= nt; ++t) b[(size_t)t] = n * (size_t)t / (size_t)nt;
-    run_threads(nt, [&](int t) { std::sort(v.begin() + b[(size_t)t], v.begin() + b[(size_t)t + 1], cmp); });
+    par_for(nt, [&](int t) { std::sort(v.begin() + b[(size_t)t], v.begin() + b[(size_t)t + 1], cmp); });
     for (int w = 1; w < nt; w *= 2) {
         std::vector<std::pair<int, int>> jobs;
         for (int t = 0; t + w < nt; t += 2 * w) jobs.push_back({t, std::min(t + 2 * w, nt)});
-        run_threads((int)jobs.size(), [&](int j) {
+        par_for((int)jobs.size(), [&](int j) {
             const int a = jobs[(size_t)j].first, m = a + w, z = jobs[(size_t)j].second;
             std::inplace_merge(v.begin() + b[(size_t)a], v.begin() + b[(size_t)m], v.begin() + b[(size_t)z], cmp);
         });
@@ -286,7 +257,7 @@ int s2a_export_owned(S2AState &S, int parts)
     std::vector<S2ARec> hdr((size_t)n);
     std::vector<int32_t> dest((size_t)n);
     const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 12) + 1));
-    run_threads(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         for (int64_t k = n * t / nt; k < n * (t + 1) / nt; ++k) {
             const int64_t rep = S.uniq[2 * k];
             S2ARec &h = hdr[(size_t)k];
@@ -313,7 +284,7 @@ int s2a_export_owned(S2AState &S, int parts)
         }
     }
     H.out.resize((size_t)base[(size_t)parts]);
-    run_threads(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         for (int64_t k = n * t / nt; k < n * (t + 1) / nt; ++k)
             put_rec(H.out.data() + at[(size_t)k], hdr[(size_t)k], S.gathered.data() + S.uniq_off[k]);
     });
@@ -427,7 +398,7 @@ int s2a_export_ranges(S2AState &S)
     }
     std::vector<uint8_t> out((size_t)base[(size_t)parts]);
     const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 12) + 1));
-    run_threads(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         for (size_t k = n * (size_t)t / (size_t)nt; k < n * (size_t)(t + 1) / (size_t)nt; ++k)
             put_rec(out.data() + at[k], *H.recs[k], rec_body(H.recs[k]));
     });
@@ -471,7 +442,7 @@ int s2a_range_format(S2AState &S, int n_names, const char *const *names, const i
     const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 12) + 1));
     std::vector<std::string> piece((size_t)nt);
     std::vector<std::vector<int64_t>> seg((size_t)nt, std::vector<int64_t>((size_t)n_names, 0));
-    run_threads(nt, [&](int t) {
+    par_for(nt, [&](int t) {
         std::string &o = piece[(size_t)t];
         for (int64_t k = n * t / nt; k < n * (t + 1) / nt; ++k) {
             const S2ARec *r = H.recs[(size_t)k];

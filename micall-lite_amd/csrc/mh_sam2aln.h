@@ -85,7 +85,6 @@ int s2a_format_units(const S2AState &S, int which, int64_t u0, int64_t u1, bool 
 int s2a_format(const S2AState &S, int which, std::vector<std::string> &out);
 // the same text written to fd from offset while it is formatted; 0 or errno
 int s2a_format_write(const S2AState &S, int which, int fd, int64_t offset, int64_t *written);
-int s2a_threads();
 // device half
 int s2a_run(Ctx &c, S2AState &S, double max_prop_n);
 

@@ -657,13 +657,11 @@ extern "C" int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, 
     S2AState &S = *ctx_of(ctx)->s2a;
     int64_t pos = offset;
     for (const std::string &piece : S.out_cache[which]) {
-        const char *p = piece.data();
-        size_t left = piece.size();
-        while (left > 0) {
-            const ssize_t w = pwrite(fd, p, left, (off_t)pos);
-            if (w <= 0) { set_error("mh_sam2aln_write: write failed (%s)", strerror(errno ? errno : EIO)); return -4; }
-            p += w; left -= (size_t)w; pos += w;
+        if (const int e = write_all_at(fd, piece.data(), piece.size(), pos)) {
+            set_error("mh_sam2aln_write: write failed (%s)", strerror(e));
+            return -4;
         }
+        pos += (int64_t)piece.size();
     }
     if (written) *written = pos - offset;
     std::vector<std::string>().swap(S.out_cache[which]);

@@ -82,18 +82,15 @@ def _declare(L):
         'mh_recs_fetch': ([_P, ctypes.c_int64, ctypes.c_int64, _P], ctypes.c_int),
         'mh_test_set_capacities': ([_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64], ctypes.c_int),
+        'mh_test_force_index_collision': ([_P, ctypes.c_int], ctypes.c_int),
         'mh_retry_counts': ([_P, _P], ctypes.c_int),
         'mh_test_set_gotoh_wait': ([_P, ctypes.c_int64], ctypes.c_int),
         'mh_format_rows': ([_P, ctypes.c_int, _P, ctypes.c_int64, ctypes.c_int64,
                             ctypes.POINTER(ctypes.c_char_p), _P, ctypes.c_size_t,
                             ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
-        'mh_write_rows': ([_P, ctypes.c_int, _P, ctypes.c_int64, ctypes.c_int64,
-                           ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, ctypes.c_int64, _I64P],
-                          ctypes.c_int),
         'mh_write_rows_crc': ([_P, ctypes.c_int, _P, ctypes.c_int64, ctypes.c_int64,
                                ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, ctypes.c_int64, _I64P,
                                ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
-        'mh_file_checksum': ([ctypes.c_int, _I64P, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         'mh_rows_load': ([_P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                           ctypes.c_int64, _P], ctypes.c_int),
         'mh_rows_load_csv': ([_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int,
@@ -104,7 +101,6 @@ def _declare(L):
         'mh_pileup_only': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P], ctypes.c_int),
         'mh_pileup_dims': ([_P, ctypes.POINTER(ctypes.c_int), _I32P, _I64P, _I64P], ctypes.c_int),
         'mh_pileup_fetch': ([_P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
-        'mh_pileup_fetch_ref': ([_P, ctypes.c_int, _P, _P, _P], ctypes.c_int),
         'mh_pileup_fetch_refs': ([_P, ctypes.c_int, _P, _P, _P, _P], ctypes.c_int),
         'mh_pileup_events': ([_P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
         'mh_pileup_exchange_bytes': ([_P, ctypes.c_int, _I64P, _I64P, _I64P], ctypes.c_int),
@@ -822,38 +818,40 @@ class Context:
         check(lib().mh_phase_times(self.h, _ptr(out), int(reset)), 'mh_phase_times')
         return dict(zip(('inflate', 'parse', 'upload', 'format', 'write'), (float(x) for x in out)))
 
+    def _row_args(self, first, n, order):
+        """What every row formatter passes on: (order pointer or None, n
+        defaulted to the rest of order / of the reads, the refname array).
+        The returned order array must outlive the call that uses the pointer."""
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            if n is None:
+                n = len(order) - first
+        elif n is None:
+            n = self.reads_count()[0] - first
+        names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
+        return order, None if order is None else _ptr(order), n, names
+
     def format_segments(self, style, order, seg_rows):
         """Format rows order[0 ..] (None: every read) in segments
         [seg_rows[s], seg_rows[s + 1]); the text stays in the library for
         write_segments.  Returns the bytes per segment (int64 array)."""
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            n = len(order)
-        else:
-            n = self.reads_count()[0]
+        order, optr, n, names = self._row_args(0, None, order)
         seg_rows = np.ascontiguousarray(seg_rows, dtype=np.int64)
         k = len(seg_rows) - 1
         out = np.zeros(max(k, 1), dtype=np.int64)
-        names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
-        check(lib().mh_format_segments(self.h, style, None if order is None else _ptr(order), n,
-                                       names, k, _ptr(seg_rows), _ptr(out)), 'mh_format_segments')
+        check(lib().mh_format_segments(self.h, style, optr, n, names, k, _ptr(seg_rows), _ptr(out)),
+              'mh_format_segments')
         return out[:k]
 
-    def write_rows_at(self, fd, offset, style, order=None):
-        """Rows order[...] (None: every read) formatted and written to
-        descriptor fd at `offset` in one stream (formatting overlapped with
-        the write); returns (bytes written, crc32)."""
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            n = len(order)
-        else:
-            n = self.reads_count()[0]
-        names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
+    def write_rows_at(self, fd, offset, style, order=None, first=0, n=None):
+        """Rows [first, first+n) (of order when given; default: every one)
+        formatted and written to descriptor fd at `offset` in one stream
+        (formatting overlapped with the write); returns (bytes written, crc32)."""
+        order, optr, n, names = self._row_args(first, n, order)
         written = ctypes.c_int64()
         crc = ctypes.c_uint32()
-        check(lib().mh_write_rows_crc(self.h, style, None if order is None else _ptr(order), 0, n,
-                                      names, int(fd), int(offset), ctypes.byref(written),
-                                      ctypes.byref(crc)), 'mh_write_rows_crc')
+        check(lib().mh_write_rows_crc(self.h, style, optr, first, n, names, int(fd), int(offset),
+                                      ctypes.byref(written), ctypes.byref(crc)), 'mh_write_rows_crc')
         return written.value, crc.value
 
     def write_segments(self, fd, offsets, crc=True):
@@ -929,6 +927,12 @@ class Context:
               'mh_test_set_capacities')
         self.map_serial += 1
 
+    def test_force_index_collision(self, on=True):
+        """Test entry point: every later index_build gets the same cache
+        signature, so only the cached bytes tell reference sets apart."""
+        check(lib().mh_test_force_index_collision(self.h, int(bool(on))),
+              'mh_test_force_index_collision')
+
     def retry_counts(self):
         """Retries taken so far: dict(cigar_pool, pileup_events, token_bytes,
         gotoh_wait)."""
@@ -966,45 +970,20 @@ class Context:
     def format_rows(self, style, first=0, n=None, order=None):
         """SAM (style 0) or CSV (style 1) text of reads [first, first+n), or
         of reads order[first:first+n] when an order is given."""
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            if n is None:
-                n = len(order) - first
-        elif n is None:
-            n = self.reads_count()[0] - first
-        names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
-        used = ctypes.c_size_t()
-        optr = None if order is None else _ptr(order)
-        # a size query formats the rows (host threads) and keeps the text;
-        # the second call copies it into a buffer of exactly that size
-        check(lib().mh_format_rows(self.h, style, optr, first, n, names, None, 0,
-                                   ctypes.byref(used)), 'mh_format_rows')
-        buf = np.empty(max(used.value, 1), dtype=np.uint8)
-        check(lib().mh_format_rows(self.h, style, optr, first, n, names, _ptr(buf), used.value,
-                                   ctypes.byref(used)), 'mh_format_rows')
-        return buf[:used.value].tobytes().decode()
+        return bytes(self.format_rows_bytes(style, first, n, order)).decode()
 
     def write_rows(self, out, style, first=0, n=None, order=None):
         """format_rows(...) written to the text file `out`.  A seekable
         UTF-8 / ASCII file that writes '\n' as is (the text is ASCII) gets
-        the rows straight from the formatting threads (mh_write_rows at its
-        file position); another file gets them through its binary buffer, a
+        the rows straight from the library (write_rows_at at its file
+        position); another file gets them through its binary buffer, a
         non-file stream as str."""
         fd = _plain_fd(out)
         if fd is not None:
-            if order is not None:
-                order = np.ascontiguousarray(order, dtype=np.int64)
-                if n is None:
-                    n = len(order) - first
-            elif n is None:
-                n = self.reads_count()[0] - first
-            names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
             out.flush()
             off = os.lseek(fd, 0, os.SEEK_CUR)
-            written = ctypes.c_int64()
-            check(lib().mh_write_rows(self.h, style, None if order is None else _ptr(order), first, n,
-                                      names, fd, off, ctypes.byref(written)), 'mh_write_rows')
-            out.seek(off + written.value)
+            written, _ = self.write_rows_at(fd, off, style, order, first, n)
+            out.seek(off + written)
             return
         text = self.format_rows_bytes(style, first, n, order)
         raw = getattr(out, 'buffer', None)
@@ -1018,15 +997,10 @@ class Context:
 
     def format_rows_bytes(self, style, first=0, n=None, order=None):
         """format_rows as a uint8 array (no str)."""
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            if n is None:
-                n = len(order) - first
-        elif n is None:
-            n = self.reads_count()[0] - first
-        names = (ctypes.c_char_p * max(self.n_refs, 1))(*[r.encode() for r in self.refnames])
+        order, optr, n, names = self._row_args(first, n, order)
         used = ctypes.c_size_t()
-        optr = None if order is None else _ptr(order)
+        # a size query formats the rows (host threads) and keeps the text;
+        # the second call copies it into a buffer of exactly that size
         check(lib().mh_format_rows(self.h, style, optr, first, n, names, None, 0,
                                    ctypes.byref(used)), 'mh_format_rows')
         buf = np.empty(max(used.value, 1), dtype=np.uint8)
@@ -1453,14 +1427,6 @@ def file_crc32(fd):
     crc = ctypes.c_uint32()
     check(lib().mh_file_crc32(fd, ctypes.byref(size), ctypes.byref(crc)), 'mh_file_crc32')
     return size.value, crc.value
-
-
-def file_checksum(fd):
-    """(size, checksum) of a whole open file: (crc32 << 32) | adler32."""
-    size = ctypes.c_int64()
-    sum_ = ctypes.c_uint64()
-    check(lib().mh_file_checksum(fd, ctypes.byref(size), ctypes.byref(sum_)), 'mh_file_checksum')
-    return size.value, sum_.value
 
 
 def levenshtein(a, b):

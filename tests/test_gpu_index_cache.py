@@ -1,9 +1,7 @@
 """The device index cache (mh_api.cpp mh_index_build) keys large reference
 sets by a 64-bit signature; a hit is used only when the cached reference
-bytes compare equal.  MH_INDEX_FORCE_COLLISION=1 gives every set the same
-signature: the second set must then be built, not served from the cache."""
-import os
-
+bytes compare equal.  Context.test_force_index_collision gives every set the
+same signature: the second set must then be built, not served from the cache."""
 import numpy as np
 import pytest
 
@@ -23,9 +21,9 @@ def test_signature_collision_rebuilds():
     seqs = [b[i % 2][300 * i:300 * i + 251] for i in range(64)]
     quals = ['I' * 251] * len(seqs)
     mode = oracle.E2E
-    os.environ['MH_INDEX_FORCE_COLLISION'] = '1'
     ctx = _native.Context(0)
     try:
+        ctx.test_force_index_collision()
         for refs in (a, b, a, b):     # every build after the first is a signature hit
             ctx.index_build(['r0', 'r1'], refs, oracle.seed_len(mode))
             ctx.reads_load(seqs, quals, False)
@@ -41,4 +39,3 @@ def test_signature_collision_rebuilds():
                 assert (got['ref'] < 0).all()
     finally:
         ctx.close()
-        del os.environ['MH_INDEX_FORCE_COLLISION']
