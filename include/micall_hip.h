@@ -29,7 +29,8 @@
  *          -> mh_gotoh_align;
  *   4. (next stage) sam2aln's Python merge of remap.csv,
  *      micall/core/sam2aln.py:395-478
- *          -> mh_sam2aln_csv, mh_sam2aln_output;
+ *          -> mh_sam2aln_csv / mh_sam2aln_csv_q (the list of q-cutoffs,
+ *             :391-402), mh_sam2aln_output;
  *   5. (the stage before) censor_fastq.censor's per-base
  *      Python loop, micall/core/censor_fastq.py:32-102
  *          -> mh_censor_fastq / mh_censor_staged, mh_censor_output /
@@ -372,7 +373,17 @@ int mh_pileup_events_import(mh_ctx *ctx, int parts, const int64_t *n_events,
  * RuntimeError) on a CIGAR apply_cigar rejects.  *n_units = matchmaker pairs. */
 int mh_sam2aln_csv(mh_ctx *ctx, const char *text, int64_t len, int q_cutoff, double max_prop_n,
                    int64_t *n_units);
-/* CSV text of the last mh_sam2aln_csv: which 0 = aligned.csv, 1 =
+/* mh_sam2aln_csv with SAM2ALN_Q_CUTOFFS as a list (sam2aln.py:25): one
+ * device pass merges every pair at each of the n_cut cutoffs (parse_sam's
+ * `for qcut in SAM2ALN_Q_CUTOFFS`, :391-402; apply_cigar and the insert rows
+ * once per pair).  aligned.csv then holds one group per (rname, qcut), a
+ * rname's groups in the order in which each cutoff first received a passing
+ * sequence (:446-452), and failed.csv one manyNs row for a pair that failed
+ * at any cutoff (:381-389).  -3, with a message, for n_cut outside 1..8, a
+ * cutoff outside 0..93 or a repeated cutoff. */
+int mh_sam2aln_csv_q(mh_ctx *ctx, const char *text, int64_t len, int n_cut, const int32_t *q_cutoffs,
+                     double max_prop_n, int64_t *n_units);
+/* CSV text of the last mh_sam2aln_csv / mh_sam2aln_csv_q: which 0 = aligned.csv, 1 =
  * insert.csv, 2 = failed.csv (DictWriter, '\n' line ends, with header).
  * buf NULL: only *used = bytes needed. */
 int mh_sam2aln_output(mh_ctx *ctx, int which, char *buf, size_t cap, size_t *used);
@@ -380,13 +391,17 @@ int mh_sam2aln_output(mh_ctx *ctx, int which, char *buf, size_t cap, size_t *use
  * 0, or 1 when the file holds '\r' (a text-mode read would translate it;
  * the caller reads the file itself), or an error. */
 int mh_sam2aln_file(mh_ctx *ctx, int fd, int q_cutoff, double max_prop_n, int64_t *n_units);
+/* mh_sam2aln_csv_q on the whole of a regular file, as mh_sam2aln_file. */
+int mh_sam2aln_file_q(mh_ctx *ctx, int fd, int n_cut, const int32_t *q_cutoffs, double max_prop_n,
+                      int64_t *n_units);
 /* Output `which` (as mh_sam2aln_output) written to fd at offset with
  * pwrite (the descriptor's own offset is not used); *written = its size.
  * Not sized before (no mh_sam2aln_output size query), it is formatted and
  * written in one pass, the writes overlapping the formatting. */
 int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *written);
-/* out[0] pairs, out[1] pairs merged on the device, out[2] distinct merged
- * sequences, out[3] failed pairs. */
+/* Of the last call of either kind: out[0] pairs, out[1] pairs merged on the
+ * device, out[2] distinct (rname, q-cutoff, merged sequence), i.e. the data
+ * rows of aligned.csv, out[3] failed pairs, i.e. the data rows of failed.csv. */
 int mh_sam2aln_stats(mh_ctx *ctx, int64_t *out4);
 /* Host wall time (ms) of the last call: [0] CSV parse + matchmaker, [1]
  * upload + device merge/group + fetch, [2..4] formatting of the three

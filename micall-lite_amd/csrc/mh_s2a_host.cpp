@@ -558,8 +558,8 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
     });
 }
 
-// aligned.csv (sam2aln.py:459-478): per rname in first-seen order, the
-// distinct merged sequences sorted by (count, gap prefix, sequence), all
+// aligned.csv (sam2aln.py:459-478): per rname in first-seen order and per
+// q-cutoff, the distinct merged sequences sorted by (count, gap prefix, sequence), all
 // descending; seq written without its leading / trailing gaps
 static void s2a_aligned(const S2AState &S, TextSink &out)
 {
@@ -568,12 +568,31 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
         std::string head("refname,qcut,rank,count,offset,seq\n");
         out.put(head);
     }
-    const int nn = (int)S.names.size();
+    const int nn = (int)S.names.size(), nc = (int)S.q_cutoffs.size();
     std::vector<int32_t> mref(S.n_merge);
     for (int64_t u = 0; u < (int64_t)S.u1.size(); ++u)
         if (S.merge_of_unit[u] >= 0) mref[S.merge_of_unit[u]] = S.name_id[u];
-    std::vector<std::vector<int64_t>> by(nn);
-    for (int64_t k = 0; k < S.n_unique; ++k) by[mref[S.uniq[2 * k]]].push_back(k);
+    // one group per (rname, cutoff k).  A rname's groups come in the order in
+    // which each cutoff first received a passing sequence (the reference's
+    // region[qcut] is created on first use, sam2aln.py:446-452): by the first
+    // merge unit that is OK at k -- merge units are in matchmaker order --
+    // then by k, the order within one pair (:391)
+    std::vector<std::vector<int64_t>> by((size_t)nn * nc);
+    for (int64_t k = 0; k < S.n_unique; ++k) {
+        const int64_t e = S.uniq[2 * k];
+        by[(size_t)mref[e / nc] * nc + e % nc].push_back(k);
+    }
+    std::vector<int64_t> first_ok((size_t)nn * nc, INT64_MAX);
+    for (int64_t e = 0; e < S.n_merge * nc; ++e)
+        if (S.res[4 * e] == S2A_OK) {
+            int64_t &f = first_ok[(size_t)mref[e / nc] * nc + e % nc];
+            f = std::min(f, e / nc);
+        }
+    std::vector<int> order((size_t)nn * nc);
+    for (int g = 0; g < nn * nc; ++g) order[g] = g;
+    for (int r = 0; r < nn; ++r)
+        std::sort(order.begin() + (size_t)r * nc, order.begin() + (size_t)(r + 1) * nc,
+                  [&](int x, int y) { return first_ok[x] != first_ok[y] ? first_ok[x] < first_ok[y] : x < y; });
     auto cmp = [&](int64_t x, int64_t y) {
         const int64_t rx = S.uniq[2 * x], ry = S.uniq[2 * y];
         const int cx = S.uniq[2 * x + 1], cy = S.uniq[2 * y + 1];
@@ -596,8 +615,10 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
                              (uint32_t)(S.res[4 * S.uniq[2 * k] + 1] ^ (int32_t)0x80000000);
     });
     auto by_key = [&](int64_t x, int64_t y) { return key[(size_t)x] > key[(size_t)y]; };
-    for (int r = 0; r < nn; ++r) {
-        auto &v = by[r];
+    for (int g : order) {
+        const int r = g / nc;
+        const int32_t qcut = S.q_cutoffs[g % nc];
+        auto &v = by[g];
         if (v.empty()) continue;
         parallel_sort(v, by_key, nt);
         std::vector<size_t> runs{0};
@@ -618,7 +639,7 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
                 const int64_t k = v[rank], rep = S.uniq[2 * k];
                 o += ref;
                 o.push_back(',');
-                put_int(o, S.q_cutoff);
+                put_int(o, qcut);
                 o.push_back(',');
                 put_int(o, rank);
                 o.push_back(',');
@@ -680,7 +701,7 @@ static void s2a_failed(const S2AState &S, TextSink &out, int64_t u0, int64_t u1,
     parallel_text(u1 - u0, s2a_threads(), out, [&](std::string &o, int64_t a, int64_t b) {
         for (int64_t u = u0 + a; u < u0 + b; ++u) {
             int cause = S.ucause[u];
-            if (cause < 0 && S.res[4 * S.merge_of_unit[u]] == S2A_MANYNS) cause = S2A_MANYNS;
+            if (cause < 0 && s2a_many_ns(S, S.merge_of_unit[u])) cause = S2A_MANYNS;
             if (cause < 0) continue;
             const int64_t r1 = S.u1[u];
             csv_field(o, S.qpool.data() + S.qoff[r1], (size_t)S.qlen[r1]);

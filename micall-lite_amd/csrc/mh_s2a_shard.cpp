@@ -449,7 +449,7 @@ int s2a_range_format(S2AState &S, int n_names, const char *const *names, const i
             const size_t before = o.size();
             o += ref[(size_t)r->gname];
             o.push_back(',');
-            put_int(o, S.q_cutoff);
+            put_int(o, S.q_cutoffs[0]);
             o.push_back(',');
             put_int(o, rank[(size_t)k]);
             o.push_back(',');
@@ -529,7 +529,7 @@ extern "C" int mh_sam2aln_part(mh_ctx *ctx, int fd, int part, int parts, int q_c
     if (int st = map_text_file(fd, &text, &len)) return st;   // 1: '\r' in it (not split)
     S2AState &S = *state_of(ctx);
     const int rc = guarded("mh_sam2aln_part", [&]() -> int {
-        S.q_cutoff = q_cutoff;
+        S.q_cutoffs.assign(1, q_cutoff);   // the sharded pass takes one q-cutoff
         S.n_merge = S.n_unique = 0;
         S.res.clear();
         for (auto &o : S.out_cache) std::vector<std::string>().swap(o);

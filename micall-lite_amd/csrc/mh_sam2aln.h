@@ -21,6 +21,8 @@ enum { S2A_OK = 0, S2A_UNMATCHED = 1, S2A_BADCIGAR = 2, S2A_2REFS = 3, S2A_MANYN
 enum { CIG_OK = 0, CIG_STAR = 1, CIG_INVALID = 2, CIG_UNSUPPORTED = 3, CIG_LONG = 4,
        CIG_SHORT = 5 };
 
+constexpr int S2A_MAX_CUTS = 8;  // q-cutoffs of one call (SAM2ALN_Q_CUTOFFS, sam2aln.py:25)
+
 struct S2AShard;                 // sam2aln split over the ranks of a job (mh_s2a_shard.cpp)
 void s2a_shard_free(S2AShard *sh);
 
@@ -50,7 +52,9 @@ struct S2AState {
     std::vector<int64_t> merge_of_unit; // index into the device merge list, -1 if none
     std::vector<int32_t> name_id;       // per unit: index into names
     std::vector<std::string> names;     // rnames in first-seen order over units
-    int q_cutoff = 15;
+    // q-cutoffs of the call, distinct, in the caller's order (sam2aln.py:391).
+    // One merge entry per (merge unit m, cutoff k): entry = m * n_cut + k
+    std::vector<int32_t> q_cutoffs{15};
     // ---- device ----
     uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_out = nullptr, *d_gather = nullptr;
     int64_t *d_soff = nullptr, *d_units = nullptr, *d_slot = nullptr, *d_goff = nullptr;
@@ -62,8 +66,8 @@ struct S2AState {
     std::unordered_map<const void *, size_t> dcap;   // bytes allocated behind each device pointer (grow-only)
     // ---- results of the device pass ----
     int64_t n_merge = 0, n_unique = 0;
-    std::vector<int32_t> res;           // per merge unit: status, offset, body_len, strip_len
-    std::vector<int32_t> uniq;          // rep merge unit, count
+    std::vector<int32_t> res;           // per entry: status, offset, body_len, strip_len
+    std::vector<int32_t> uniq;          // rep entry, count
     std::vector<int64_t> uniq_off;      // offsets into gathered
     TextBuf gathered;                   // bodies of the distinct sequences (not zero-filled)
     // ---- formatted outputs (cached between the size query and the copy) ----
@@ -75,6 +79,16 @@ struct S2AState {
     S2AShard *shard = nullptr;
     ~S2AState() { if (shard) s2a_shard_free(shard); }
 };
+
+// failed.csv's manyNs of merge unit m: any of its entries failed the prop_N
+// test (parse_sam keeps one failure cause per pair, sam2aln.py:381-389)
+inline bool s2a_many_ns(const S2AState &S, int64_t m)
+{
+    const int64_t nc = (int64_t)S.q_cutoffs.size();
+    for (int64_t e = m * nc; e < (m + 1) * nc; ++e)
+        if (S.res[4 * e] == S2A_MANYNS) return true;
+    return false;
+}
 
 // host half: the header row of text, then its records (body_lo >= 0: only
 // the records in bytes [body_lo, body_hi) of text, both record boundaries)

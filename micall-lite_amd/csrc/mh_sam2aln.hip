@@ -6,13 +6,16 @@
 //          the row-level failure causes of parse_sam (:340-348) and the
 //          apply_cigar checks that raise (:113-151); insert.csv / failed.csv
 //          text and the final ordering of aligned.csv (:465-478)
-//   k_s2a_merge   one wave64 per pair: apply_cigar of both mates into LDS,
-//                 merge_pairs (q_cutoff 15, no insertions, :156-237)
-//                 lane-parallel, prop_N test (:381-385), the merged sequence
-//                 written to HBM and hashed (two 64-bit position-keyed sums)
-//   k_s2a_count   one thread per merged pair: open-addressing table keyed by
-//                 the hash, count + first unit per distinct sequence
-//   k_s2a_verify  one wave per merged pair: every member of a group is
+//   k_s2a_merge   one wave64 per pair: apply_cigar of both mates into LDS
+//                 once, then for each of the call's n_cut q-cutoffs (:391-402)
+//                 merge_pairs (no insertions, :156-237) lane-parallel, the
+//                 prop_N test (:381-385), the merged sequence written to HBM
+//                 and hashed (two 64-bit position-keyed sums).  One "merge
+//                 entry" is (pair, cutoff k): entry = pair * n_cut + k
+//   k_s2a_count   one thread per entry: open-addressing table keyed by
+//                 the hash, count + first entry per distinct sequence of a
+//                 group (rname, cutoff)
+//   k_s2a_verify  one wave per entry: every member of a group is
 //                 compared byte for byte with the group's first member
 //                 (a hash collision is reported, never merged silently)
 //   k_s2a_gather  distinct sequences copied out for the host's sort
@@ -70,14 +73,15 @@ struct S2AArgs {
     const uint32_t *cig;
     const int64_t *units;     // per merge unit: row1, row2 (-1: single)
     const int32_t *uref;
-    const int64_t *slot;      // byte offset of the unit's output slot in out
+    const int64_t *slot;      // byte offset of each entry's output slot in out
     int64_t n;
-    int q_cutoff;
+    int n_cut;                // merge entry e = unit * n_cut + k
+    unsigned char cut[S2A_MAX_CUTS];   // q_cutoff + 33 of cutoff k
     double max_prop_n;
     int span_cap, ops_cap, wave_bytes;
     uint8_t *out;
-    int32_t *res;             // 4 per unit
-    uint64_t *h;              // 2 per unit
+    int32_t *res;             // 4 per entry
+    uint64_t *h;              // 2 per entry
     int32_t *ctr;             // [0] error
 };
 
@@ -103,32 +107,58 @@ struct Mate {
     char *c, *q;             // LDS: c[t], q[t] for t < rf
 };
 
-// merged character at padded position i (sam2aln.py:186-230); seq1 = a,
-// seq2 = b (the longer padded read); single = no mate
-__device__ __forceinline__ char s2a_char(int i, const Mate &a, const Mate &b, bool single,
-                                         int rev_start, unsigned char cut)
+// merge_pairs (sam2aln.py:186-230) at padded position i, for every cutoff at
+// once; seq1 = a, seq2 = b (the longer padded read); single = no mate.  The
+// merged character is thr > cut ? ch : 'N' for every cut, with (ch, thr)
+// fixed for the pair (q and cut compared as bytes, cut = q_cutoff + 33):
+//   - cutoff-independent characters ('-', 'n', the 'N' of a quality tie, an
+//     unpaired read) get thr = S2A_ALWAYS, above every cut (cut <= 93 + 33);
+//   - mates agree:  q1 > cut || q2 > cut          ==  max(q1, q2) > cut;
+//   - mates disagree by >= 5:  q1 > max(q2, cut) ? c1 : q2 > max(q1, cut) ? c2 : 'N'.
+//     With q1 > q2 the second test is false, so it is q1 > cut ? c1 : 'N';
+//     with q2 > q1 the first is false, so it is q2 > cut ? c2 : 'N';
+//   - past the shorter mate: q2 > cut ? c2 : 'N'.
+constexpr unsigned char S2A_ALWAYS = 255;
+
+__device__ __forceinline__ void s2a_pos(int i, const Mate &a, const Mate &b, bool single,
+                                        int rev_start, char &ch, unsigned char &thr)
 {
     char c2 = '-';
     unsigned char q2 = '!';
     if (i >= b.pad && i < b.len) { c2 = b.c[i - b.pad]; q2 = (unsigned char)b.q[i - b.pad]; }
-    if (single) return c2;
+    ch = c2;
+    thr = S2A_ALWAYS;
+    if (single) return;
     if (i < a.len) {
         char c1 = '-';
         unsigned char q1 = '!';
         if (i >= a.pad) { c1 = a.c[i - a.pad]; q1 = (unsigned char)a.q[i - a.pad]; }
-        if (c1 == '-' && c2 == '-') return '-';
-        if (c1 == c2) return (q1 > cut || q2 > cut) ? c1 : 'N';
-        const int dq = (int)q2 - (int)q1;
-        if ((dq < 0 ? -dq : dq) >= 5) {
-            const unsigned char m2 = q2 > cut ? q2 : cut, m1 = q1 > cut ? q1 : cut;
-            return q1 > m2 ? c1 : (q2 > m1 ? c2 : 'N');
+        if (c1 == c2) {
+            if (c1 != '-') thr = q1 > q2 ? q1 : q2;
+            return;
         }
-        return 'N';
+        const int dq = (int)q2 - (int)q1;
+        if (dq >= 5) { thr = q2; return; }
+        if (dq <= -5) { ch = c1; thr = q1; return; }
+        ch = 'N';
+        return;
     }
-    if (c2 == '-') return i >= rev_start ? '-' : 'n';
-    return q2 > cut ? c2 : 'N';
+    if (c2 == '-') { ch = i >= rev_start ? '-' : 'n'; return; }
+    thr = q2;
 }
 
+// NC: compile-time bound on A.n_cut (1, 2, 4 or 8), so that the per-cutoff
+// accumulators below are registers, never scratch memory.  Everything up to
+// and including the forward / reverse start scans runs once per pair; each
+// cutoff then costs one compare per position.
+//
+// offset and stripped length are computed per cutoff (first[k], last[k]),
+// not shared.  A '-' that apply_cigar or the padding wrote can never win a
+// cutoff-dependent position -- its quality is ' ' or '!', above no cut >= '!'
+// -- but the parser admits any byte in the seq column, and a '-' the read
+// itself holds comes with the read's own quality: it wins (a gap) at a low
+// cutoff and is 'N' at a higher one, which moves first and last.
+template <int NC>
 __global__ __launch_bounds__(256) void k_s2a_merge(S2AArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -139,7 +169,10 @@ __global__ __launch_bounds__(256) void k_s2a_merge(S2AArgs A)
     char *cq = (char *)wb;                                     // c0 q0 c1 q1, span_cap each
     int32_t *opref = (int32_t *)(wb + 4 * (size_t)A.span_cap); // ops_cap + 1 per mate
     int32_t *opread = opref + 2 * (A.ops_cap + 1);
-    const unsigned char cut = (unsigned char)(A.q_cutoff + 33);
+    const int n_cut = NC == 1 ? 1 : A.n_cut;
+    unsigned char cut[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) cut[k] = A.cut[k];
 
     for (int64_t u = (int64_t)blockIdx.x * wpb + wv; u < A.n; u += (int64_t)gridDim.x * wpb) {
         const int64_t rows[2] = {A.units[2 * u], A.units[2 * u + 1]};
@@ -250,65 +283,99 @@ __global__ __launch_bounds__(256) void k_s2a_merge(S2AArgs A)
         // starting drops positions < len(seq1), sam2aln.py:191-195)
         const int ibase = fwd ? 0 : a.len;
         const int mlen = len2 - ibase;
-        // ---- offset (leading '-'), last non-'-', count of 'N' ----
-        int first = 1 << 30, last = -1, nN = 0;
+        // ---- per cutoff: offset (leading '-'), last non-'-', count of 'N' ----
+        int first[NC], last[NC], nN[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) { first[k] = 1 << 30; last[k] = -1; nN[k] = 0; }
         for (int j0 = 0; j0 < mlen; j0 += 64) {
             const int j = j0 + lane;
             if (j < mlen) {
                 const int i = j + ibase;
-                char m;
-                if (!single && fwd && i < fwd_start) m = '-';
-                else m = s2a_char(i, a, b, single, rev_start, cut);
-                if (m != '-') { first = min(first, j); last = max(last, j); }
-                nN += m == 'N';
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            first = min(first, __shfl_xor(first, o, 64));
-            last = max(last, __shfl_xor(last, o, 64));
-            nN += __shfl_xor(nN, o, 64);
-        }
-        int status = S2A_OK;
-        if (last < 0) {
-            status = S2A_EMPTY;   // len(mseq.strip('-')) == 0: ZeroDivisionError in the reference
-        } else {
-            const double prop = (double)nN / (double)(last - first + 1);
-            if (prop > A.max_prop_n) status = S2A_MANYNS;
-        }
-        const int off = status == S2A_EMPTY ? 0 : first;
-        const int blen = status == S2A_EMPTY ? 0 : mlen - first;
-        uint64_t h1 = 0, h2 = 0;
-        if (status == S2A_OK) {
-            uint8_t *dst = A.out + A.slot[u];
-            for (int j0 = 0; j0 < blen; j0 += 64) {
-                const int jj = j0 + lane;
-                if (jj < blen) {
-                    const int i = jj + off + ibase;
-                    const char m = (!single && fwd && i < fwd_start)
-                                       ? '-' : s2a_char(i, a, b, single, rev_start, cut);
-                    dst[jj] = (uint8_t)m;
-                    const uint64_t k1 = mix64(2ull * (uint64_t)jj + 1ull) | 1ull;
-                    const uint64_t k2 = mix64((uint64_t)jj ^ 0x5bd1e995ull << 32) | 1ull;
-                    h1 += k1 * (uint64_t)(uint8_t)m;
-                    h2 += k2 * (uint64_t)(uint8_t)m;
+                char ch = '-';
+                unsigned char thr = S2A_ALWAYS;
+                if (single || !fwd || i >= fwd_start) s2a_pos(i, a, b, single, rev_start, ch, thr);
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    const char m = thr > cut[k] ? ch : 'N';
+                    if (m != '-') { first[k] = min(first[k], j); last[k] = max(last[k], j); }
+                    nN[k] += m == 'N';
                 }
             }
-            for (int o = 32; o > 0; o >>= 1) {
-                h1 += __shfl_xor(h1, o, 64);
-                h2 += __shfl_xor(h2, o, 64);
-            }
-            const uint64_t meta = ((uint64_t)(uint32_t)A.uref[u] << 40) ^
-                                  ((uint64_t)(uint32_t)off << 20) ^ (uint64_t)(uint32_t)blen;
-            h1 = mix64(h1 ^ mix64(meta));
-            h2 = mix64(h2 + 0x2545f4914f6cdd1dull * mix64(meta + 7));
         }
-        if (lane == 0) {
-            A.res[4 * u] = status;
-            A.res[4 * u + 1] = off;
-            A.res[4 * u + 2] = blen;
-            A.res[4 * u + 3] = last < 0 ? 0 : last - first + 1;
-            A.h[2 * u] = h1;
-            A.h[2 * u + 1] = h2;
+        int status[NC], off[NC], blen[NC];
+        uint64_t h1[NC], h2[NC];
+        int lo = 1 << 30;           // smallest offset of the cutoffs that passed
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            for (int o = 32; o > 0; o >>= 1) {
+                first[k] = min(first[k], __shfl_xor(first[k], o, 64));
+                last[k] = max(last[k], __shfl_xor(last[k], o, 64));
+                nN[k] += __shfl_xor(nN[k], o, 64);
+            }
+            status[k] = S2A_OK;
+            if (last[k] < 0) {
+                status[k] = S2A_EMPTY;   // len(mseq.strip('-')) == 0: ZeroDivisionError in the reference
+            } else {
+                const double prop = (double)nN[k] / (double)(last[k] - first[k] + 1);
+                if (prop > A.max_prop_n) status[k] = S2A_MANYNS;
+            }
+            off[k] = status[k] == S2A_EMPTY ? 0 : first[k];
+            blen[k] = status[k] == S2A_EMPTY ? 0 : mlen - first[k];
+            h1[k] = h2[k] = 0;
+            if (k < n_cut && status[k] == S2A_OK) lo = min(lo, off[k]);
+        }
+        // ---- the bodies of the cutoffs that passed, each into its entry's
+        // slot, and their hashes: (ch, thr) once per position ----
+        const int64_t e0 = u * n_cut;
+        int64_t slot[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) slot[k] = k < n_cut ? A.slot[e0 + k] : 0;
+        for (int j0 = lo; j0 < mlen; j0 += 64) {
+            const int j = j0 + lane;
+            if (j < mlen) {
+                const int i = j + ibase;
+                char ch = '-';
+                unsigned char thr = S2A_ALWAYS;
+                if (single || !fwd || i >= fwd_start) s2a_pos(i, a, b, single, rev_start, ch, thr);
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                    if (k < n_cut && status[k] == S2A_OK && j >= off[k]) {
+                        const char m = thr > cut[k] ? ch : 'N';
+                        const int jj = j - off[k];
+                        A.out[slot[k] + jj] = (uint8_t)m;
+                        const uint64_t k1 = mix64(2ull * (uint64_t)jj + 1ull) | 1ull;
+                        const uint64_t k2 = mix64((uint64_t)jj ^ 0x5bd1e995ull << 32) | 1ull;
+                        h1[k] += k1 * (uint64_t)(uint8_t)m;
+                        h2[k] += k2 * (uint64_t)(uint8_t)m;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            if (k >= n_cut) break;
+            if (status[k] == S2A_OK) {
+                for (int o = 32; o > 0; o >>= 1) {
+                    h1[k] += __shfl_xor(h1[k], o, 64);
+                    h2[k] += __shfl_xor(h2[k], o, 64);
+                }
+                // the group of a sequence is (rname, cutoff): equal bodies at
+                // two cutoffs are two rows of aligned.csv
+                const uint64_t grp = (uint64_t)(uint32_t)A.uref[u] * (uint64_t)n_cut + (uint64_t)k;
+                const uint64_t meta = (grp << 40) ^ ((uint64_t)(uint32_t)off[k] << 20) ^
+                                      (uint64_t)(uint32_t)blen[k];
+                h1[k] = mix64(h1[k] ^ mix64(meta));
+                h2[k] = mix64(h2[k] + 0x2545f4914f6cdd1dull * mix64(meta + 7));
+            }
+            if (lane == 0) {
+                const int64_t e = e0 + k;
+                A.res[4 * e] = status[k];
+                A.res[4 * e + 1] = off[k];
+                A.res[4 * e + 2] = blen[k];
+                A.res[4 * e + 3] = last[k] < 0 ? 0 : last[k] - first[k] + 1;
+                A.h[2 * e] = h1[k];
+                A.h[2 * e + 1] = h2[k];
+            }
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -340,7 +407,7 @@ __global__ __launch_bounds__(256) void k_s2a_count(const int32_t *res, const uin
 
 __global__ __launch_bounds__(256) void k_s2a_verify(const int32_t *res, const uint64_t *h,
                                                     const int32_t *uref, const int64_t *slot,
-                                                    const uint8_t *out, int64_t n,
+                                                    const uint8_t *out, int64_t n, int n_cut,
                                                     const uint64_t *tkey, const int32_t *trep,
                                                     uint64_t mask, int32_t *ctr)
 {
@@ -354,7 +421,9 @@ __global__ __launch_bounds__(256) void k_s2a_verify(const int32_t *res, const ui
         while (tkey[s] != key) s = (s + 1) & mask;
         const int64_t r = trep[s];
         if (r == u) continue;
-        bool bad = h[2 * r + 1] != h[2 * u + 1] || uref[r] != uref[u] ||
+        // same group: same rname and same cutoff (entry = unit * n_cut + k)
+        bool bad = h[2 * r + 1] != h[2 * u + 1] || uref[r / n_cut] != uref[u / n_cut] ||
+                   r % n_cut != u % n_cut ||
                    res[4 * r + 1] != res[4 * u + 1] || res[4 * r + 2] != res[4 * u + 2];
         if (!bad) {
             const uint8_t *x = out + slot[u], *y = out + slot[r];
@@ -438,7 +507,8 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
     const int64_t nu = (int64_t)S.u1.size();
     std::vector<int64_t> mu;      // row pairs of merged units
     std::vector<int32_t> mref;
-    std::vector<int64_t> slot;
+    std::vector<int64_t> slot;    // one per entry
+    const int nc = (int)S.q_cutoffs.size();
     int64_t total = 0;
     int span_cap = 1, ops_cap = 1;
     for (int64_t u = 0; u < nu; ++u) {
@@ -463,8 +533,10 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
             span_cap = std::max(span_cap, rf);
             ops_cap = std::max(ops_cap, S.n_cig[r]);
         }
-        slot.push_back(total);
-        total += std::max(0, hi - lo);
+        for (int k = 0; k < nc; ++k) {
+            slot.push_back(total);
+            total += std::max(0, hi - lo);
+        }
     }
     S.n_merge = (int64_t)mref.size();
     S.n_unique = 0;
@@ -473,6 +545,11 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
     S.uniq_off.clear();
     S.gathered.clear();
     if (S.n_merge == 0) return 0;
+    if (S.n_merge * nc > 0x7f7f7f7f) {   // entries are int32 in the table and in uniq
+        set_error("sam2aln: %lld pairs at %d q-cutoffs are too many merge entries",
+                  (long long)S.n_merge, nc);
+        return -3;
+    }
     span_cap = (span_cap + 15) & ~15;
     const int wave_bytes = ((4 * span_cap + 2 * 4 * 2 * (ops_cap + 1)) + 15) & ~15;
     int wpb = 4;
@@ -491,42 +568,46 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
     if (int st = s2a_upload(S, S.d_units, mu, s)) return st;
     if (int st = s2a_upload(S, S.d_uref, mref, s)) return st;
     if (int st = s2a_upload(S, S.d_slot, slot, s)) return st;
-    const int64_t nm = S.n_merge;
+    const int64_t nm = S.n_merge, ne = nm * nc;   // pairs, entries
     uint64_t tsize = 1024;
-    while (tsize < (uint64_t)(2 * nm)) tsize <<= 1;
+    while (tsize < (uint64_t)(2 * ne)) tsize <<= 1;
     if (int st = dev_reserve(S, S.d_out, total > 0 ? (size_t)total : 1)) return st;
-    if (int st = dev_reserve(S, S.d_res, sizeof(int32_t) * 4 * nm)) return st;
-    if (int st = dev_reserve(S, S.d_h, sizeof(uint64_t) * 2 * nm)) return st;
+    if (int st = dev_reserve(S, S.d_res, sizeof(int32_t) * 4 * ne)) return st;
+    if (int st = dev_reserve(S, S.d_h, sizeof(uint64_t) * 2 * ne)) return st;
     if (int st = dev_reserve(S, S.d_ctr, sizeof(int32_t) * 4)) return st;
     if (int st = dev_reserve(S, S.d_tkey, sizeof(uint64_t) * tsize)) return st;
     if (int st = dev_reserve(S, S.d_tcnt, sizeof(int32_t) * tsize)) return st;
     if (int st = dev_reserve(S, S.d_trep, sizeof(int32_t) * tsize)) return st;
-    if (int st = dev_reserve(S, S.d_uniq, sizeof(int32_t) * 2 * nm)) return st;
+    if (int st = dev_reserve(S, S.d_uniq, sizeof(int32_t) * 2 * ne)) return st;
     MH_HIP(hipMemsetAsync(S.d_ctr, 0, sizeof(int32_t) * 4, s));
     MH_HIP(hipMemsetAsync(S.d_tkey, 0, sizeof(uint64_t) * tsize, s));
     MH_HIP(hipMemsetAsync(S.d_tcnt, 0, sizeof(int32_t) * tsize, s));
     MH_HIP(hipMemsetAsync(S.d_trep, 0x7f, sizeof(int32_t) * tsize, s));
 
     S2AArgs a{S.d_seq, S.d_qual, S.d_soff, S.d_pos, S.d_cigoff, S.d_ncig, S.d_cig,
-              S.d_units, S.d_uref, S.d_slot, nm, S.q_cutoff, max_prop_n, span_cap, ops_cap,
+              S.d_units, S.d_uref, S.d_slot, nm, nc, {}, max_prop_n, span_cap, ops_cap,
               wave_bytes, S.d_out, S.d_res, S.d_h, S.d_ctr};
+    for (int k = 0; k < nc; ++k) a.cut[k] = (unsigned char)(S.q_cutoffs[k] + 33);
     int64_t blocks = (nm + wpb - 1) / wpb;
     if (blocks > 256 * 64) blocks = 256 * 64;
-    MH_HIP(hipFuncSetAttribute((const void *)k_s2a_merge,
+    // the instance whose compile-time bound is the next power of two >= nc
+    void (*merge)(S2AArgs) = nc == 1 ? k_s2a_merge<1> : nc == 2 ? k_s2a_merge<2>
+                             : nc <= 4 ? k_s2a_merge<4> : k_s2a_merge<8>;
+    MH_HIP(hipFuncSetAttribute((const void *)merge,
                                hipFuncAttributeMaxDynamicSharedMemorySize, wpb * wave_bytes));
     const int p0 = prof_begin(c, "k_s2a_merge");
-    hipLaunchKernelGGL(k_s2a_merge, dim3((unsigned)blocks), dim3(64 * wpb), wpb * wave_bytes, s, a);
+    hipLaunchKernelGGL(merge, dim3((unsigned)blocks), dim3(64 * wpb), wpb * wave_bytes, s, a);
     prof_end(c, p0);
     MH_HIP(hipGetLastError());
-    int64_t tb = (nm + 255) / 256;
+    int64_t tb = (ne + 255) / 256;
     if (tb > 65536) tb = 65536;
     const int p1 = prof_begin(c, "k_s2a_group");
-    hipLaunchKernelGGL(k_s2a_count, dim3((unsigned)tb), dim3(256), 0, s, S.d_res, S.d_h, nm,
+    hipLaunchKernelGGL(k_s2a_count, dim3((unsigned)tb), dim3(256), 0, s, S.d_res, S.d_h, ne,
                        S.d_tkey, S.d_tcnt, S.d_trep, tsize - 1);
-    int64_t vb = (nm + 3) / 4;
+    int64_t vb = (ne + 3) / 4;
     if (vb > 256 * 64) vb = 256 * 64;
     hipLaunchKernelGGL(k_s2a_verify, dim3((unsigned)vb), dim3(256), 0, s, S.d_res, S.d_h, S.d_uref,
-                       S.d_slot, S.d_out, nm, S.d_tkey, S.d_trep, tsize - 1, S.d_ctr);
+                       S.d_slot, S.d_out, ne, nc, S.d_tkey, S.d_trep, tsize - 1, S.d_ctr);
     int64_t cb = (int64_t)((tsize + 255) / 256);
     if (cb > 65536) cb = 65536;
     hipLaunchKernelGGL(k_s2a_compact, dim3((unsigned)cb), dim3(256), 0, s, S.d_tkey, S.d_tcnt,
@@ -541,17 +622,17 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
         return -4;
     }
     S.n_unique = ctr[1];
-    S.res.resize(4 * nm);
+    S.res.resize(4 * ne);
     S.uniq.resize(2 * (size_t)S.n_unique);
-    MH_HIP(hipMemcpyAsync(S.res.data(), S.d_res, sizeof(int32_t) * 4 * nm, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(S.res.data(), S.d_res, sizeof(int32_t) * 4 * ne, hipMemcpyDeviceToHost, s));
     if (S.n_unique)
         MH_HIP(hipMemcpyAsync(S.uniq.data(), S.d_uniq, sizeof(int32_t) * 2 * S.n_unique,
                               hipMemcpyDeviceToHost, s));
     MH_HIP(hipStreamSynchronize(s));
-    for (int64_t u = 0; u < nm; ++u)
-        if (S.res[4 * u] == S2A_EMPTY) {
+    for (int64_t e = 0; e < ne; ++e)
+        if (S.res[4 * e] == S2A_EMPTY) {
             set_error("sam2aln: merged sequence of unit %lld is all gaps (float division by zero)",
-                      (long long)u);
+                      (long long)(e / nc));
             return -3;
         }
     // gather the distinct bodies
@@ -582,15 +663,37 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
 
 using namespace mh;
 
-extern "C" int mh_sam2aln_csv(mh_ctx *ctx, const char *text, int64_t len, int q_cutoff,
-                              double max_prop_n, int64_t *n_units)
+// the list of q-cutoffs of a call: 1..S2A_MAX_CUTS distinct values in 0..93
+static int s2a_check_cutoffs(int n_cut, const int32_t *q_cutoffs)
 {
-    if (!ctx || (!text && len) || len < 0 || q_cutoff < 0 || q_cutoff > 93) return -3;
+    if (n_cut < 1 || n_cut > S2A_MAX_CUTS || !q_cutoffs) {
+        set_error("sam2aln: %d q-cutoffs (1..%d are supported)", n_cut, S2A_MAX_CUTS);
+        return -3;
+    }
+    for (int k = 0; k < n_cut; ++k) {
+        if (q_cutoffs[k] < 0 || q_cutoffs[k] > 93) {
+            set_error("sam2aln: q-cutoff %d outside 0..93", (int)q_cutoffs[k]);
+            return -3;
+        }
+        for (int j = 0; j < k; ++j)
+            if (q_cutoffs[j] == q_cutoffs[k]) {
+                set_error("sam2aln: q-cutoff %d given twice", (int)q_cutoffs[k]);
+                return -3;
+            }
+    }
+    return 0;
+}
+
+extern "C" int mh_sam2aln_csv_q(mh_ctx *ctx, const char *text, int64_t len, int n_cut,
+                                const int32_t *q_cutoffs, double max_prop_n, int64_t *n_units)
+{
+    if (!ctx || (!text && len) || len < 0) return -3;
+    if (int st = s2a_check_cutoffs(n_cut, q_cutoffs)) return st;
     Ctx &c = *ctx_of(ctx);
     MH_HIP(hipSetDevice(c.device));
     if (!c.s2a) c.s2a = new S2AState();
     S2AState &S = *c.s2a;
-    S.q_cutoff = q_cutoff;
+    S.q_cutoffs.assign(q_cutoffs, q_cutoffs + n_cut);
     S.n_merge = S.n_unique = 0;
     S.res.clear();
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
@@ -619,15 +722,30 @@ extern "C" int mh_sam2aln_csv(mh_ctx *ctx, const char *text, int64_t len, int q_
     return 0;
 }
 
-extern "C" int mh_sam2aln_file(mh_ctx *ctx, int fd, int q_cutoff, double max_prop_n, int64_t *n_units)
+extern "C" int mh_sam2aln_csv(mh_ctx *ctx, const char *text, int64_t len, int q_cutoff,
+                              double max_prop_n, int64_t *n_units)
+{
+    const int32_t q = q_cutoff;
+    return mh_sam2aln_csv_q(ctx, text, len, 1, &q, max_prop_n, n_units);
+}
+
+extern "C" int mh_sam2aln_file_q(mh_ctx *ctx, int fd, int n_cut, const int32_t *q_cutoffs,
+                                 double max_prop_n, int64_t *n_units)
 {
     if (!ctx || fd < 0) return -3;
+    if (int st = s2a_check_cutoffs(n_cut, q_cutoffs)) return st;
     const char *text = nullptr;
     size_t len = 0;
     if (int st = map_text_file(fd, &text, &len)) return st;
-    const int rc = mh_sam2aln_csv(ctx, text, (int64_t)len, q_cutoff, max_prop_n, n_units);
+    const int rc = mh_sam2aln_csv_q(ctx, text, (int64_t)len, n_cut, q_cutoffs, max_prop_n, n_units);
     unmap_text_file(text, len);
     return rc;
+}
+
+extern "C" int mh_sam2aln_file(mh_ctx *ctx, int fd, int q_cutoff, double max_prop_n, int64_t *n_units)
+{
+    const int32_t q = q_cutoff;
+    return mh_sam2aln_file_q(ctx, fd, 1, &q, max_prop_n, n_units);
 }
 
 extern "C" int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *written)
@@ -720,7 +838,7 @@ extern "C" int mh_sam2aln_stats(mh_ctx *ctx, int64_t *out4)
     const S2AState &S = *c.s2a;
     int64_t nfail = 0;
     for (int64_t u = 0; u < (int64_t)S.u1.size(); ++u)
-        if (S.ucause[u] >= 0 || S.res[4 * S.merge_of_unit[u]] != S2A_OK) ++nfail;
+        if (S.ucause[u] >= 0 || s2a_many_ns(S, S.merge_of_unit[u])) ++nfail;
     out4[0] = (int64_t)S.u1.size();
     out4[1] = S.n_merge;
     out4[2] = S.n_unique;

@@ -122,6 +122,9 @@ def _declare(L):
                                      ctypes.c_int64], ctypes.c_int),
         'mh_sam2aln_csv': ([_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                             _I64P], ctypes.c_int),
+        'mh_sam2aln_csv_q': ([_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_double,
+                              _I64P], ctypes.c_int),
+        'mh_sam2aln_file_q': ([_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_double, _I64P], ctypes.c_int),
         'mh_sam2aln_output': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _I64P], ctypes.c_int),
@@ -335,21 +338,33 @@ class Context:
         check(lib().mh_ctx_sync(self.h), 'mh_ctx_sync')
 
     # ---- sam2aln --------------------------------------------------------
-    def sam2aln_csv(self, text, q_cutoff=15, max_prop_n=0.5):
+    def sam2aln_csv(self, text, q_cutoff=15, max_prop_n=0.5, q_cutoffs=None):
         """mh_sam2aln_csv on remap.csv text (str or bytes); returns the
-        number of matchmaker pairs."""
+        number of matchmaker pairs.  q_cutoffs (a list of 1..8 distinct
+        cutoffs, mh_sam2aln_csv_q) wins over q_cutoff when given."""
         data = text.encode() if isinstance(text, str) else bytes(text)
         n = ctypes.c_int64()
+        if q_cutoffs is not None:
+            cuts = np.ascontiguousarray(q_cutoffs, dtype=np.int32)
+            check(lib().mh_sam2aln_csv_q(self.h, data, len(data), len(cuts), _ptr(cuts),
+                                         float(max_prop_n), ctypes.byref(n)), 'mh_sam2aln_csv_q')
+            return n.value
         check(lib().mh_sam2aln_csv(self.h, data, len(data), int(q_cutoff), float(max_prop_n),
                                    ctypes.byref(n)), 'mh_sam2aln_csv')
         return n.value
 
-    def sam2aln_file(self, fd, q_cutoff=15, max_prop_n=0.5):
+    def sam2aln_file(self, fd, q_cutoff=15, max_prop_n=0.5, q_cutoffs=None):
         """mh_sam2aln_file on the whole regular file fd (mmap'd): the number of
         matchmaker pairs, or None when the file holds '\r' (read it in text
-        mode and use sam2aln_csv)."""
+        mode and use sam2aln_csv).  q_cutoffs as in sam2aln_csv
+        (mh_sam2aln_file_q)."""
         n = ctypes.c_int64()
-        st = lib().mh_sam2aln_file(self.h, int(fd), int(q_cutoff), float(max_prop_n), ctypes.byref(n))
+        if q_cutoffs is not None:
+            cuts = np.ascontiguousarray(q_cutoffs, dtype=np.int32)
+            st = lib().mh_sam2aln_file_q(self.h, int(fd), len(cuts), _ptr(cuts), float(max_prop_n),
+                                         ctypes.byref(n))
+        else:
+            st = lib().mh_sam2aln_file(self.h, int(fd), int(q_cutoff), float(max_prop_n), ctypes.byref(n))
         if st == 1:
             return None
         check(st, 'mh_sam2aln_file')

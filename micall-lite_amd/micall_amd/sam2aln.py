@@ -2,8 +2,9 @@
 Drop-in for micall/core/sam2aln.py: same function, arguments and output files.
 
 sam2aln() reads remap.csv, pairs rows by qname, merges each pair into one
-sequence in consensus coordinates (apply_cigar + merge_pairs at q-cutoff 15),
-drops pairs with more than half of their bases censored, and writes the
+sequence in consensus coordinates (apply_cigar, then merge_pairs at each of
+SAM2ALN_Q_CUTOFFS, all in one device pass), drops pairs with more than half
+of their bases censored, and writes the
 distinct merged sequences with their counts per reference (aligned.csv), the
 insertions the merge removed (insert.csv) and the pairs that failed
 (failed.csv) -- sam2aln.py:395-478.  The per-pair work and the count of
@@ -16,7 +17,8 @@ merges its pairs on its GPU, and writes its own insert.csv / failed.csv rows
 and its piece of aligned.csv at all-gathered offsets; the distinct merged
 sequences are counted by hash owner and sorted across the ranks by a sample
 sort (_sam2aln_sharded, mh_s2a_shard.cpp) -- the reference's own pool splits
-parse_sam over pairs the same way (sam2aln.py:411-424).
+parse_sam over pairs the same way (sam2aln.py:411-424).  The split takes one
+q-cutoff; with more, rank 0 does the whole stage.
 """
 import argparse
 
@@ -26,21 +28,38 @@ from . import session
 
 SAM2ALN_Q_CUTOFFS = [15]  # sam2aln.py:24
 MAX_PROP_N = 0.5          # sam2aln.py:25
+MAX_Q_CUTOFFS = 8         # distinct cutoffs of one device pass (mh_sam2aln_csv_q)
 
 
 SHARD_STATS = {}   # how the last sharded call ran (tests): mode, rows parsed
 
 
-def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None):
-    """sam2aln.sam2aln (sam2aln.py:395-478).  In a sharded job every rank
-    does its share (_sam2aln_sharded); when remap.csv cannot be split that
-    way, rank 0 computes and writes while the other ranks wait
-    (session.writer_stage)."""
-    if len(SAM2ALN_Q_CUTOFFS) != 1:
-        raise NotImplementedError('the device merge takes one q-cutoff per pass')
+def _cutoff_list(q_cutoffs):
+    """The distinct cutoffs in first-seen order: the reference keeps one
+    merged sequence per cutoff in a dict (mseqs[qcut], sam2aln.py:402), so a
+    repeated cutoff changes nothing."""
+    cuts = []
+    for q in SAM2ALN_Q_CUTOFFS if q_cutoffs is None else q_cutoffs:
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+            raise ValueError('q-cutoff {!r} is not an integer'.format(q))
+        if int(q) not in cuts:
+            cuts.append(int(q))
+    if not 1 <= len(cuts) <= MAX_Q_CUTOFFS:
+        raise ValueError('{} distinct q-cutoffs: the device merge takes 1 to {}'.format(
+            len(cuts), MAX_Q_CUTOFFS))
+    return cuts
+
+
+def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None):
+    """sam2aln.sam2aln (sam2aln.py:395-478).  q_cutoffs: the list of quality
+    cutoffs, None for the module's SAM2ALN_Q_CUTOFFS (where the reference's
+    users set it).  In a sharded job every rank does its share
+    (_sam2aln_sharded); when remap.csv cannot be split that way, rank 0
+    computes and writes while the other ranks wait (session.writer_stage)."""
+    cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
-    if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv):
+    if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts):
         return
     with session.writer_stage(aligned_csv, insert_csv, failed_csv) as stage:
         if not stage.active:
@@ -49,12 +68,12 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
         fd = session.readable_fd(remap_csv)
         done = None
         if fd is not None:   # the file mmap'd by the library (no '\r' in it)
-            done = ctx.sam2aln_file(fd, q_cutoff=SAM2ALN_Q_CUTOFFS[0], max_prop_n=MAX_PROP_N)
+            done = ctx.sam2aln_file(fd, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
             if done is not None:
                 remap_csv.seek(0, 2)     # consumed, as the reference's DictReader leaves it
         if done is None:
             text = session.read_text(remap_csv)
-            ctx.sam2aln_csv(text, q_cutoff=SAM2ALN_Q_CUTOFFS[0], max_prop_n=MAX_PROP_N)
+            ctx.sam2aln_csv(text, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
                 _write_output(ctx, which, handle)
@@ -63,11 +82,16 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
 SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitters
 
 
-def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv):
+def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None):
     """This rank's share of sam2aln.  False (on every rank, before any
-    output is written) when the job must fall back to rank 0 alone: a
-    remap.csv that is not a plain file on every rank, one with quoted fields
-    or '\r', or a qname whose rows sit on two ranks."""
+    output is written) when the job must fall back to rank 0 alone: more
+    than one q-cutoff (every rank holds the same list, so none has to ask),
+    a remap.csv that is not a plain file on every rank, one with quoted
+    fields or '\r', or a qname whose rows sit on two ranks."""
+    if cuts is None:
+        cuts = _cutoff_list(None)
+    if len(cuts) != 1:
+        return False
     from . import sharded_io
     from .sharded_io import SharedOutput, _agree_ok, _checked
     ctx = session.context()
@@ -75,7 +99,7 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv):
     if not _agree_ok(sh, fd is not None):
         return False
     sh.barrier()             # every rank opened (truncated) the outputs
-    part = _checked(sh, lambda: ctx.sam2aln_part(fd, sh.rank, sh.world, SAM2ALN_Q_CUTOFFS[0],
+    part = _checked(sh, lambda: ctx.sam2aln_part(fd, sh.rank, sh.world, cuts[0],
                                                   MAX_PROP_N))
     if not _agree_ok(sh, part is not None):
         return False
@@ -164,13 +188,16 @@ def parseArgs():
     parser.add_argument('failed_csv', nargs='?', default=None, type=argparse.FileType('w'),
                         help='<output> CSV containing reads that failed to merge')
     parser.add_argument('-p', type=int, default=None, help='(optional) number of threads')
+    parser.add_argument('--qcut', type=int, action='append', default=None, metavar='Q',
+                        help='quality cutoff of the merge; repeat it for several '
+                             '(default: {})'.format(' '.join(map(str, SAM2ALN_Q_CUTOFFS))))
     return parser.parse_args()
 
 
 def main():
     args = parseArgs()
     sam2aln(remap_csv=args.remap_csv, aligned_csv=args.aligned_csv, insert_csv=args.insert_csv,
-            failed_csv=args.failed_csv, nthreads=args.p)
+            failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut)
 
 
 if __name__ == '__main__':
