@@ -30,7 +30,8 @@
  *   4. (next stage) sam2aln's Python merge of remap.csv,
  *      micall/core/sam2aln.py:395-478
  *          -> mh_sam2aln_csv / mh_sam2aln_csv_q (the list of q-cutoffs,
- *             :391-402), mh_sam2aln_output;
+ *             :391-402), mh_sam2aln_output; mh_sam2aln_resident when the
+ *             rows are the records of the mapping pass still on the device;
  *   5. (the stage before) censor_fastq.censor's per-base
  *      Python loop, micall/core/censor_fastq.py:32-102
  *          -> mh_censor_fastq / mh_censor_staged, mh_censor_output /
@@ -394,6 +395,22 @@ int mh_sam2aln_file(mh_ctx *ctx, int fd, int q_cutoff, double max_prop_n, int64_
 /* mh_sam2aln_csv_q on the whole of a regular file, as mh_sam2aln_file. */
 int mh_sam2aln_file_q(mh_ctx *ctx, int fd, int n_cut, const int32_t *q_cutoffs, double max_prop_n,
                       int64_t *n_units);
+/* sam2aln over the records of the last mh_map and the resident reads (what
+ * remap() wrote as remap.csv, one row per read in read order), merged at
+ * n_cut cutoffs as mh_sam2aln_csv_q; refnames = the @SQ names of that pass.
+ * The rows are built on the device (k_s2a_stage) instead of parsed and
+ * uploaded; the outputs are those of mh_sam2aln_csv_q on that file.
+ * -3 with a message when no mapping pass or no read names are resident.
+ * 1 (nothing computed) when such a file's rows would pair otherwise than
+ * the reads do -- mates with two QNAMEs, or unpaired reads whose QNAMEs may
+ * repeat: the caller parses the file. */
+int mh_sam2aln_resident(mh_ctx *ctx, int n_refs, const char *const *refnames, int n_cut,
+                        const int32_t *q_cutoffs, double max_prop_n, int64_t *n_units);
+/* Test entry point: SEQ / QUAL of rows [first, first + n) as the last
+ * mh_sam2aln_resident staged them, back to back, with their lengths.
+ * *used = the bytes of either; seq NULL only sizes. */
+int mh_sam2aln_resident_rows(mh_ctx *ctx, int64_t first, int64_t n, int32_t *len,
+                             uint8_t *seq, uint8_t *qual, size_t cap, size_t *used);
 /* Output `which` (as mh_sam2aln_output) written to fd at offset with
  * pwrite (the descriptor's own offset is not used); *written = its size.
  * Not sized before (no mh_sam2aln_output size query), it is formatted and
@@ -403,9 +420,10 @@ int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *wr
  * device, out[2] distinct (rname, q-cutoff, merged sequence), i.e. the data
  * rows of aligned.csv, out[3] failed pairs, i.e. the data rows of failed.csv. */
 int mh_sam2aln_stats(mh_ctx *ctx, int64_t *out4);
-/* Host wall time (ms) of the last call: [0] CSV parse + matchmaker, [1]
- * upload + device merge/group + fetch, [2..4] formatting of the three
- * outputs (0 until formatted). */
+/* Host wall time (ms) of the last call: [0] CSV parse + matchmaker (unit
+ * building for mh_sam2aln_resident), [1] upload (the stage kernel for
+ * mh_sam2aln_resident) + device merge/group + fetch, [2..4] formatting of
+ * the three outputs (0 until formatted). */
 int mh_sam2aln_timing(mh_ctx *ctx, double *ms5);
 
 /* ---- sam2aln split over the ranks of a job (same reference call,

@@ -1448,6 +1448,25 @@ struct BaseTables {
 };
 static const BaseTables kBases;
 
+extern "C++" {
+namespace mh {
+int host_read_text(Ctx &c0, int64_t r, bool rev, char *seq, char *qual)
+{
+    const CtxEx &c = static_cast<const CtxEx &>(c0);
+    if (r < 0 || (size_t)r >= c.host.len.size() || (size_t)r >= c.host.off.size()) return -1;
+    const int L = c.host.len[r];
+    if (!seq || !qual) return L;
+    const uint8_t *s = c.host.seq.data() + c.host.off[r], *q = c.host.qual.data() + c.host.off[r];
+    for (int x = 0; x < L; ++x) {
+        const int y = rev ? L - 1 - x : x;
+        seq[y] = rev ? kBases.rc[s[x]] : kBases.fw[s[x]];
+        qual[y] = (char)q[x];
+    }
+    return L;
+}
+}  // namespace mh
+}  // extern "C++"
+
 // One row of SAM (style 0) or CSV (style 1) text, appended to out at *used
 // (out grows as needed; it is not zero-filled beyond what is written).
 static void format_row(const CtxEx *c, int style, const Rec &a, int64_t r, const uint32_t *pool,

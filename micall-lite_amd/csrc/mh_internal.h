@@ -355,6 +355,11 @@ struct Ctx {
 };
 
 void set_error(const char *fmt, ...);
+// SEQ / QUAL of read r as the SAM rows print them (ACGTN; reversed and
+// complemented when rev) written to seq / qual from the host copy of the
+// reads; returns the read's length (nothing written when seq is null), -1
+// when the context keeps no text for r
+int host_read_text(Ctx &c, int64_t r, bool rev, char *seq, char *qual);
 Ctx *ctx_of(mh_ctx *ctx);          // the context behind a C-ABI handle
 void s2a_free(Ctx &c);
 void censor_free(Ctx &c);

@@ -3,6 +3,8 @@
 //               parallel chunks split at record boundaries; matchmaker
 //               (:291-312); parse_sam's row-level causes (:340-348) and the
 //               apply_cigar checks that raise (:113-151)
+//   s2a_units_resident  the same units, causes and names for rows that are
+//               the resident reads and records (mh_sam2aln_resident): no text
 //   s2a_format  aligned.csv (:459-478), insert.csv (:357-380, :446-447),
 //               failed.csv (:387-389, :449-450) as DictWriter writes them
 // Threads: min(16, hardware threads, OMP_NUM_THREADS); output is identical
@@ -748,6 +750,133 @@ int s2a_format_write(const S2AState &S, int which, int fd, int64_t offset, int64
     s2a_emit(S, which, sink);
     if (written) *written = sink.pos - offset;
     return sink.err;
+}
+
+// ---------------------------------------------------------------------------
+// units of the resident rows (mh_sam2aln_resident)
+// ---------------------------------------------------------------------------
+// What s2a_parse derives from remap.csv, for a file that holds every
+// resident read once in read order: matchmaker (sam2aln.py:291-312) pairs
+// rows by QNAME, so with mates interleaved unit p is rows (2p, 2p + 1) as
+// long as the two mates share their QNAME, and unpaired reads with distinct
+// QNAMEs are all left over, in read order, as (row, None).
+int s2a_units_resident(Ctx &c, S2AState &S, int n_refs, const char *const *refnames,
+                       const std::vector<int32_t> &sam_ref, const std::vector<int32_t> &span_ins)
+{
+    const auto tp = std::chrono::steady_clock::now();
+    const NameTable &names = c.names;
+    const int64_t nr = S.n_rows;
+    const bool paired = c.reads.paired != 0;
+    const int nt = std::max(1, std::min(s2a_threads(), (int)(nr >> 14) + 1));
+    // ---- may the rows stand for matchmaker's units? ----
+    std::atomic<int> differs(0);
+    if (paired) {
+        par_for(nt, [&](int t) {
+            for (int64_t p = (nr / 2) * t / nt; p < (nr / 2) * (t + 1) / nt; ++p)
+                if (names[2 * p] != names[2 * p + 1]) { differs = 1; return; }
+        });
+    } else {
+        // distinct QNAMEs: no two equal hashes (equal hashes of two distinct
+        // names send the call to the file path too, which is always right)
+        std::vector<int64_t> h((size_t)nr);
+        par_for(nt, [&](int t) {
+            for (int64_t r = nr * t / nt; r < nr * (t + 1) / nt; ++r)
+                h[(size_t)r] = (int64_t)hash_bytes(names[r].data(), names[r].size());
+        });
+        parallel_sort(h, [](int64_t a, int64_t b) { return a < b; }, nt);
+        for (int64_t r = 1; r < nr; ++r)
+            if (h[(size_t)r] == h[(size_t)r - 1]) { differs = 1; break; }
+    }
+    if (differs) return 1;
+    s2a_mark(tp, "resident pairing");
+    // ---- QNAMEs and RNAMEs (every per-row array is written by the threads below) ----
+    S.qpool.resize(names.pool.size());
+    S.qoff.resize(nr); S.qlen.resize(nr); S.rid.resize(nr);
+    S.coff.resize(nr); S.clen.resize(nr); S.cpool.clear();
+    S.cstate.resize(nr); S.qshort.resize(nr);
+    S.soff.resize(nr); S.slen.resize(nr);
+    // RNAME ids as the parser gives them: equal names share one id; '*' last
+    S.rnames.clear();
+    std::unordered_map<std::string, int> gid;
+    std::vector<int32_t> rid_of_ref((size_t)n_refs + 1);
+    for (int k = 0; k <= n_refs; ++k) {
+        const std::string name(k < n_refs ? refnames[k] : "*");
+        auto it = gid.emplace(name, (int)S.rnames.size());
+        if (it.second) S.rnames.push_back(name);
+        rid_of_ref[k] = it.first->second;
+    }
+    std::atomic<int> bad_ref(0);
+    par_for(nt, [&](int t) {
+        const size_t q0 = names.pool.size() * (size_t)t / (size_t)nt,
+                     q1 = names.pool.size() * (size_t)(t + 1) / (size_t)nt;
+        if (q1 > q0) memcpy(S.qpool.data() + q0, names.pool.data() + q0, q1 - q0);
+        for (int64_t r = nr * t / nt; r < nr * (t + 1) / nt; ++r) {
+            S.coff[r] = 0; S.clen[r] = 0; S.qshort[r] = 0; S.soff[r] = 0; S.slen[r] = 0;
+            S.qoff[r] = names.off[r];
+            S.qlen[r] = (int32_t)(names.off[r + 1] - names.off[r]);
+            const int32_t sr = sam_ref[r];
+            if (sr >= n_refs) { bad_ref = 1; return; }
+            S.rid[r] = rid_of_ref[sr >= 0 ? sr : n_refs];
+            S.cstate[r] = span_ins[r] < 0 ? CIG_STAR : CIG_OK;
+        }
+    });
+    if (bad_ref) {
+        set_error("mh_sam2aln_resident: a record names a reference outside the %d given", n_refs);
+        return -3;
+    }
+    s2a_mark(tp, "resident rows");
+    // ---- units, parse_sam's early causes and the rname order ----
+    const int64_t nu = paired ? nr / 2 : nr;
+    S.u1.resize(nu); S.u2.resize(nu);
+    S.ucause.assign(nu, -1);
+    S.upaired.assign(nu, 0);
+    S.merge_of_unit.assign(nu, -1);
+    S.name_id.assign(nu, 0);
+    S.names.clear();
+    std::vector<int32_t> nid_of_rid(S.rnames.size(), -1);
+    for (int64_t u = 0; u < nu; ++u) {
+        const int64_t r1 = paired ? 2 * u : u, r2 = paired ? 2 * u + 1 : -1;
+        S.u1[u] = r1;
+        S.u2[u] = r2;
+        int32_t &n = nid_of_rid[S.rid[r1]];
+        if (n < 0) { n = (int32_t)S.names.size(); S.names.push_back(S.rnames[S.rid[r1]]); }
+        S.name_id[u] = n;
+        const int pr = S.flag[r1] & 1;
+        S.upaired[u] = (int8_t)pr;
+        int cause = -1;
+        if (pr && r2 < 0) cause = S2A_UNMATCHED;
+        else if (S.cstate[r1] == CIG_STAR || (r2 >= 0 && S.cstate[r2] == CIG_STAR)) cause = S2A_BADCIGAR;
+        else if (pr && S.rid[r1] != S.rid[r2]) cause = S2A_2REFS;
+        S.ucause[u] = (int8_t)cause;
+    }
+    s2a_mark(tp, "resident units");
+    // ---- SEQ / QUAL on the host: only the rows insert.csv quotes from ----
+    std::vector<int64_t> ins_rows;
+    int64_t text = 0;
+    for (int64_t r = 0; r < nr; ++r) {
+        if (span_ins[r] < 0 || !(span_ins[r] & 1)) continue;
+        const int L = host_read_text(c, r, false, nullptr, nullptr);
+        if (L < 0) {
+            set_error("mh_sam2aln_resident: the reads' text is not kept on the host");
+            return -3;
+        }
+        ins_rows.push_back(r);
+        S.soff[r] = text;
+        S.slen[r] = L;
+        text += L;
+    }
+    S.seq.resize((size_t)text);
+    S.qual.resize((size_t)text);
+    const int64_t ni = (int64_t)ins_rows.size();
+    par_for(std::max(1, std::min(nt, (int)(ni >> 10) + 1)), [&](int t) {
+        const int n = std::max(1, std::min(nt, (int)(ni >> 10) + 1));
+        for (int64_t k = ni * t / n; k < ni * (t + 1) / n; ++k) {
+            const int64_t r = ins_rows[(size_t)k];
+            host_read_text(c, r, (span_ins[r] & 2) != 0, S.seq.data() + S.soff[r], S.qual.data() + S.soff[r]);
+        }
+    });
+    s2a_mark(tp, "resident insert rows");
+    return 0;
 }
 
 }  // namespace mh

@@ -63,6 +63,11 @@ struct S2AState {
             *d_ctr = nullptr;
     uint32_t *d_cig = nullptr;
     uint64_t *d_h = nullptr, *d_tkey = nullptr;
+    // per read, written by k_s2a_stage (mh_sam2aln_resident): FLAG, the
+    // index of RNAME (-1: '*') and reference span << 2 | reversed << 1 | has an I op
+    // (-1: unmapped)
+    int32_t *d_flag = nullptr, *d_samref = nullptr, *d_spanins = nullptr;
+    int64_t staged_reads = -1;          // reads whose SEQ / QUAL d_seq / d_qual hold as staged; -1 none
     std::unordered_map<const void *, size_t> dcap;   // bytes allocated behind each device pointer (grow-only)
     // ---- results of the device pass ----
     int64_t n_merge = 0, n_unique = 0;
@@ -99,7 +104,24 @@ int s2a_format_units(const S2AState &S, int which, int64_t u0, int64_t u1, bool 
 int s2a_format(const S2AState &S, int which, std::vector<std::string> &out);
 // the same text written to fd from offset while it is formatted; 0 or errno
 int s2a_format_write(const S2AState &S, int which, int fd, int64_t offset, int64_t *written);
-// device half
-int s2a_run(Ctx &c, S2AState &S, double max_prop_n);
+// device half.  dev: the row arrays are on the device already (k_s2a_stage
+// wrote them) and span[r] is row r's reference span; without it they are
+// uploaded from S and the spans come from S.cig
+struct S2ADevRows {
+    const uint8_t *seq, *qual;
+    const int64_t *soff;
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int32_t *span;                // host: S2AState::d_spanins per row
+};
+int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev = nullptr);
+// Units, failure causes, group names and QNAMEs of the resident rows (one
+// per read, in read order) instead of s2a_parse: S.pos, S.flag, S.n_cig,
+// S.cig_off and S.cig hold the rows as k_s2a_stage wrote them; sam_ref[r]
+// indexes refnames (-1: '*'), span_ins[r] as S2ADevRows::span.  1 when the
+// rows cannot stand for matchmaker's pairing of the file (mates with two
+// QNAMEs, an unpaired QNAME that may repeat): the caller parses the file.
+int s2a_units_resident(Ctx &c, S2AState &S, int n_refs, const char *const *refnames,
+                       const std::vector<int32_t> &sam_ref, const std::vector<int32_t> &span_ins);
 
 }  // namespace mh

@@ -19,6 +19,9 @@
 //                 compared byte for byte with the group's first member
 //                 (a hash collision is reported, never merged silently)
 //   k_s2a_gather  distinct sequences copied out for the host's sort
+//   k_s2a_stage   mh_sam2aln_resident: the rows k_s2a_merge reads, built from
+//                 the resident packed reads and the last mapping pass's
+//                 records instead of parsed from remap.csv and uploaded
 // Bit-for-bit specification: the reference itself (tests/golden/e2e/*/aligned.csv
 // etc. were produced by running micall.core.sam2aln on the same remap.csv).
 #include <fcntl.h>
@@ -46,6 +49,9 @@ static void s2a_free_device(S2AState &S)
     hipFree(S.d_pos); hipFree(S.d_cigoff); hipFree(S.d_ncig);
     hipFree(S.d_uref); hipFree(S.d_res); hipFree(S.d_tcnt); hipFree(S.d_trep);
     hipFree(S.d_uniq); hipFree(S.d_ctr); hipFree(S.d_cig); hipFree(S.d_h); hipFree(S.d_tkey);
+    hipFree(S.d_flag); hipFree(S.d_samref); hipFree(S.d_spanins);
+    S.d_flag = S.d_samref = S.d_spanins = nullptr;
+    S.staged_reads = -1;
     S.d_seq = S.d_qual = S.d_out = S.d_gather = nullptr;
     S.d_soff = S.d_units = S.d_slot = S.d_goff = nullptr;
     S.d_pos = S.d_cigoff = S.d_ncig = S.d_uref = S.d_res = S.d_tcnt = S.d_trep =
@@ -465,6 +471,127 @@ __global__ __launch_bounds__(256) void k_s2a_gather(const int32_t *uniq, const i
 }
 
 // ---------------------------------------------------------------------------
+// k_s2a_stage: the resident reads and records as the rows of remap.csv.
+// For read r the SEQ and QUAL bytes format_row prints (ACGTN, reversed and
+// complemented on the reverse strand of a mapped read) go to seq / qual at
+// the read's own padded offset R.off[r] (a multiple of 32, so S2AArgs.soff
+// is R.off and every 16-byte store is aligned); POS, the CIGAR's place in the
+// mapping pass's pool, FLAG and RNAME's index go to the row arrays, and the
+// reference span (M + D), the strand and "has an I op" to span_ins for the
+// host's slots.
+//
+// 16 lanes per read, one 16-base chunk per lane and step: a chunk is one
+// 2-bit word, half an N-mask word and 16 quality bytes in, two 16-byte
+// stores out, and the 16 lanes of a read write 256 consecutive bytes.  A
+// reversed chunk reads its 16 source bases backwards from the read's end
+// (an unaligned window over two words, shifted into place) and writes
+// forwards like any other.
+// ---------------------------------------------------------------------------
+struct StageArgs {
+    DevReads R;
+    const Rec *rec;
+    const uint32_t *pool;
+    uint8_t *seq, *qual;
+    int32_t *pos, *cig_off, *n_cig, *flag, *sam_ref, *span_ins;
+};
+
+// 16 2-bit codes (base i at bits 2i) and their N bits -> 16 ASCII bytes
+__device__ __forceinline__ uint4 s2a_ascii16(uint32_t codes, uint32_t nm)
+{
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int i = 4 * k + b;
+            uint32_t ch = (0x54474341u >> (8 * ((codes >> (2 * i)) & 3u))) & 0xffu;   // "ACGT"
+            if ((nm >> i) & 1u) ch = 'N';
+            v |= ch << (8 * b);
+        }
+        w[k] = v;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// bytes s .. s + 7 of the 16 bytes (x, y), s in 0..7
+__device__ __forceinline__ uint64_t s2a_funnel(uint64_t x, uint64_t y, int s)
+{
+    return s ? (x >> (8 * s)) | (y << (64 - 8 * s)) : x;
+}
+
+__global__ __launch_bounds__(256) void k_s2a_stage(StageArgs A)
+{
+    const int sub = threadIdx.x & 15;
+    const int64_t ngrp = (int64_t)gridDim.x * 16;
+    for (int64_t r = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); r < A.R.n; r += ngrp) {
+        const Rec *a = A.rec + r;
+        const int ref = a->ref, ncg = ref >= 0 ? a->n_cigar : 0, coff = a->cig_off;
+        const bool rev = ref >= 0 && a->rev;
+        const int L = A.R.len[r];
+        const int64_t off = A.R.off[r];
+        // ---- reference span and insertion flag: the read's ops over its lanes ----
+        int span = 0, ins = 0;
+        for (int o = sub; o < ncg; o += 16) {
+            const uint32_t op = A.pool[coff + o];
+            const int t = (int)(op & 15);
+            if (t == MH_OP_M || t == MH_OP_D) span += (int)(op >> 4);
+            ins |= t == MH_OP_I;
+        }
+        for (int o = 8; o > 0; o >>= 1) {
+            span += __shfl_xor(span, o, 16);
+            ins |= __shfl_xor(ins, o, 16);
+        }
+        if (sub == 0) {
+            A.pos[r] = a->sam_pos;
+            A.cig_off[r] = coff;
+            A.n_cig[r] = ncg;
+            A.flag[r] = a->flag;
+            A.sam_ref[r] = a->sam_ref;
+            A.span_ins[r] = ref >= 0 ? (span << 2 | (rev ? 2 : 0) | ins) : -1;
+        }
+        // ---- SEQ and QUAL, 16 bases per lane ----
+        const uint32_t *w2 = A.R.seq2 + (off >> 4), *wn = A.R.nmask + (off >> 5);
+        const uint8_t *q = A.R.qual + off;
+        const int nch = (L + 15) >> 4;
+        for (int j = sub; j < nch; j += 16) {
+            uint32_t codes, nm;
+            uint4 qv;
+            if (!rev) {
+                codes = w2[j];
+                nm = (wn[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+                qv = *(const uint4 *)(q + 16 * j);
+            } else {
+                // output bases 16j .. 16j+15 are source bases lo+15 .. lo, lo >= -15
+                const int lo = L - 16 - 16 * j;
+                const int qw = (lo + 16) >> 4, sh = lo & 15;
+                const uint32_t cl = qw >= 1 ? w2[qw - 1] : 0u, chh = w2[qw];
+                uint32_t x = (uint32_t)((((uint64_t)chh << 32) | cl) >> (2 * sh));
+                x = __brev(x);                                           // base order reversed,
+                x = ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u); // each code's bits back in order
+                codes = ~x;                                              // complement: 3 - code
+                const int qn = (lo + 32) >> 5, shn = (lo + 32) & 31;
+                const uint32_t ml = qn >= 1 ? wn[qn - 1] : 0u, mh = wn[qn];
+                nm = __brev((uint32_t)((((uint64_t)mh << 32) | ml) >> shn) & 0xffffu) >> 16;
+                const uint4 z = make_uint4(0, 0, 0, 0);
+                const uint4 va = qw >= 1 ? *(const uint4 *)(q + 16 * (qw - 1)) : z;
+                const uint4 vb = *(const uint4 *)(q + 16 * qw);
+                const uint64_t a0 = (uint64_t)va.y << 32 | va.x, a1 = (uint64_t)va.w << 32 | va.z;
+                const uint64_t b0 = (uint64_t)vb.y << 32 | vb.x, b1 = (uint64_t)vb.w << 32 | vb.z;
+                const bool up = sh >= 8;
+                const int s8 = sh & 7;
+                const uint64_t r0 = s2a_funnel(up ? a1 : a0, up ? b0 : a1, s8);
+                const uint64_t r1 = s2a_funnel(up ? b0 : a1, up ? b1 : b0, s8);
+                const uint64_t o0 = __builtin_bswap64(r1), o1 = __builtin_bswap64(r0);
+                qv = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+            }
+            *(uint4 *)(A.seq + off + 16 * j) = s2a_ascii16(codes, nm);
+            *(uint4 *)(A.qual + off + 16 * j) = qv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 // a device buffer of at least `bytes` behind p: kept between calls and
@@ -501,7 +628,7 @@ static int s2a_upload_bytes(S2AState &S, uint8_t *&dst, const Bytes &v, hipStrea
 
 // apply_cigar's checks on one row (sam2aln.py:113-151): the regex, the
 // supported ops and the read length; the reference raises RuntimeError.
-int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
+int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
 {
     hipStream_t s = c.stream;
     const int64_t nu = (int64_t)S.u1.size();
@@ -522,8 +649,8 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
         int hi = 0, lo = 1 << 30;
         for (int64_t r : {r1, r2}) {
             if (r < 0) continue;
-            int rf = 0;
-            for (int o = 0; o < S.n_cig[r]; ++o) {
+            int rf = dev ? dev->span[r] >> 2 : 0;
+            for (int o = 0; !dev && o < S.n_cig[r]; ++o) {
                 const uint32_t op = S.cig[S.cig_off[r] + o];
                 if ((op & 15) == MH_OP_M || (op & 15) == MH_OP_D) rf += (int)(op >> 4);
             }
@@ -558,13 +685,16 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
         set_error("sam2aln: reference span %d too long for LDS", span_cap);
         return -3;
     }
-    if (int st = s2a_upload_bytes(S, S.d_seq, S.seq, s)) return st;
-    if (int st = s2a_upload_bytes(S, S.d_qual, S.qual, s)) return st;
-    if (int st = s2a_upload(S, S.d_soff, S.soff, s)) return st;
-    if (int st = s2a_upload(S, S.d_pos, S.pos, s)) return st;
-    if (int st = s2a_upload(S, S.d_cigoff, S.cig_off, s)) return st;
-    if (int st = s2a_upload(S, S.d_ncig, S.n_cig, s)) return st;
-    if (int st = s2a_upload(S, S.d_cig, S.cig, s)) return st;
+    if (!dev) {
+        S.staged_reads = -1;     // d_seq / d_qual hold the file's rows from here on
+        if (int st = s2a_upload_bytes(S, S.d_seq, S.seq, s)) return st;
+        if (int st = s2a_upload_bytes(S, S.d_qual, S.qual, s)) return st;
+        if (int st = s2a_upload(S, S.d_soff, S.soff, s)) return st;
+        if (int st = s2a_upload(S, S.d_pos, S.pos, s)) return st;
+        if (int st = s2a_upload(S, S.d_cigoff, S.cig_off, s)) return st;
+        if (int st = s2a_upload(S, S.d_ncig, S.n_cig, s)) return st;
+        if (int st = s2a_upload(S, S.d_cig, S.cig, s)) return st;
+    }
     if (int st = s2a_upload(S, S.d_units, mu, s)) return st;
     if (int st = s2a_upload(S, S.d_uref, mref, s)) return st;
     if (int st = s2a_upload(S, S.d_slot, slot, s)) return st;
@@ -584,8 +714,10 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n)
     MH_HIP(hipMemsetAsync(S.d_tcnt, 0, sizeof(int32_t) * tsize, s));
     MH_HIP(hipMemsetAsync(S.d_trep, 0x7f, sizeof(int32_t) * tsize, s));
 
-    S2AArgs a{S.d_seq, S.d_qual, S.d_soff, S.d_pos, S.d_cigoff, S.d_ncig, S.d_cig,
-              S.d_units, S.d_uref, S.d_slot, nm, nc, {}, max_prop_n, span_cap, ops_cap,
+    S2AArgs a{dev ? dev->seq : S.d_seq, dev ? dev->qual : S.d_qual, dev ? dev->soff : S.d_soff,
+              dev ? dev->pos : S.d_pos, dev ? dev->cig_off : S.d_cigoff,
+              dev ? dev->n_cig : S.d_ncig, dev ? dev->cig : S.d_cig, S.d_units, S.d_uref,
+              S.d_slot, nm, nc, {}, max_prop_n, span_cap, ops_cap,
               wave_bytes, S.d_out, S.d_res, S.d_h, S.d_ctr};
     for (int k = 0; k < nc; ++k) a.cut[k] = (unsigned char)(S.q_cutoffs[k] + 33);
     int64_t blocks = (nm + wpb - 1) / wpb;
@@ -698,6 +830,7 @@ extern "C" int mh_sam2aln_csv_q(mh_ctx *ctx, const char *text, int64_t len, int 
     S.res.clear();
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
     S.out_valid = 0;
+    S.staged_reads = -1;
     auto t0 = std::chrono::steady_clock::now();
     int pst = 0;
     try {
@@ -727,6 +860,151 @@ extern "C" int mh_sam2aln_csv(mh_ctx *ctx, const char *text, int64_t len, int q_
 {
     const int32_t q = q_cutoff;
     return mh_sam2aln_csv_q(ctx, text, len, 1, &q, max_prop_n, n_units);
+}
+
+// the row arrays of every resident read from the records of the last mapping
+// pass (k_s2a_stage), their host copies in S and in sam_ref / span_ins
+static int s2a_stage(Ctx &c, S2AState &S, std::vector<int32_t> &sam_ref, std::vector<int32_t> &span_ins)
+{
+    hipStream_t s = c.stream;
+    const DevReads &R = c.reads;
+    const int64_t n = R.n;
+    const size_t rows = sizeof(int32_t) * (size_t)(n > 0 ? n : 1);
+    S.staged_reads = -1;
+    if (int st = dev_reserve(S, S.d_seq, (size_t)R.total_bases + 64)) return st;
+    if (int st = dev_reserve(S, S.d_qual, (size_t)R.total_bases + 64)) return st;
+    if (int st = dev_reserve(S, S.d_pos, rows)) return st;
+    if (int st = dev_reserve(S, S.d_cigoff, rows)) return st;
+    if (int st = dev_reserve(S, S.d_ncig, rows)) return st;
+    if (int st = dev_reserve(S, S.d_flag, rows)) return st;
+    if (int st = dev_reserve(S, S.d_samref, rows)) return st;
+    if (int st = dev_reserve(S, S.d_spanins, rows)) return st;
+    S.n_rows = n;
+    S.pos.resize(n); S.cig_off.resize(n); S.n_cig.resize(n); S.flag.resize(n);
+    sam_ref.resize(n); span_ins.resize(n);
+    const int64_t used = c.map.last_cigar < c.map.pool_cap ? c.map.last_cigar : c.map.pool_cap;
+    S.cig.resize(used > 0 ? (size_t)used : 0);
+    if (n == 0) return 0;
+    StageArgs a{R, c.map.rec, c.map.pool, S.d_seq, S.d_qual, S.d_pos, S.d_cigoff, S.d_ncig,
+                S.d_flag, S.d_samref, S.d_spanins};
+    int64_t blocks = (n + 15) / 16;
+    if (blocks > (1 << 20)) blocks = 1 << 20;
+    const int p0 = prof_begin(c, "k_s2a_stage");
+    hipLaunchKernelGGL(k_s2a_stage, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    prof_end(c, p0);
+    MH_HIP(hipGetLastError());
+    const size_t nb = sizeof(int32_t) * (size_t)n;
+    MH_HIP(hipMemcpyAsync(S.pos.data(), S.d_pos, nb, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(S.cig_off.data(), S.d_cigoff, nb, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(S.n_cig.data(), S.d_ncig, nb, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(S.flag.data(), S.d_flag, nb, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(sam_ref.data(), S.d_samref, nb, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(span_ins.data(), S.d_spanins, nb, hipMemcpyDeviceToHost, s));
+    if (used > 0)
+        MH_HIP(hipMemcpyAsync(S.cig.data(), c.map.pool, sizeof(uint32_t) * (size_t)used,
+                              hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    S.staged_reads = n;
+    return 0;
+}
+
+extern "C" int mh_sam2aln_resident(mh_ctx *ctx, int n_refs, const char *const *refnames, int n_cut,
+                                   const int32_t *q_cutoffs, double max_prop_n, int64_t *n_units)
+{
+    if (!ctx || n_refs < 0 || (n_refs > 0 && !refnames)) return -3;
+    if (int st = s2a_check_cutoffs(n_cut, q_cutoffs)) return st;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    if (!c.map.valid || c.map.n_reads != c.reads.n) {
+        set_error("mh_sam2aln_resident: no mapping pass is resident (call mh_map)");
+        return -3;
+    }
+    if ((int64_t)c.names.size() != c.reads.n) {
+        set_error("mh_sam2aln_resident: no read names are resident");
+        return -3;
+    }
+    if (n_refs != c.map.n_refs) {
+        set_error("mh_sam2aln_resident: %d reference names for a pass over %d references", n_refs,
+                  c.map.n_refs);
+        return -3;
+    }
+    if (!c.s2a) c.s2a = new S2AState();
+    S2AState &S = *c.s2a;
+    S.q_cutoffs.assign(q_cutoffs, q_cutoffs + n_cut);
+    S.n_merge = S.n_unique = 0;
+    S.res.clear();
+    for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
+    S.out_valid = 0;
+    S.u1.clear();
+    std::vector<int32_t> sam_ref, span_ins;
+    int st = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto t1 = t0, t2 = t0;
+    try {
+        st = s2a_stage(c, S, sam_ref, span_ins);
+        t1 = std::chrono::steady_clock::now();
+        if (!st) st = s2a_units_resident(c, S, n_refs, refnames, sam_ref, span_ins);
+        t2 = std::chrono::steady_clock::now();
+        if (!st) {
+            const S2ADevRows dev{S.d_seq, S.d_qual, c.reads.off, S.d_pos, S.d_cigoff, S.d_ncig,
+                                 c.map.pool, span_ins.data()};
+            st = s2a_run(c, S, max_prop_n, &dev);
+        }
+    } catch (const std::exception &e) {
+        set_error("mh_sam2aln_resident: out of memory (%s)", e.what());
+        st = -2;
+    }
+    if (st) {
+        S.u1.clear();
+        return st;
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    S.t_parse = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    S.t_device = std::chrono::duration<double, std::milli>((t1 - t0) + (t3 - t2)).count();
+    if (n_units) *n_units = (int64_t)S.u1.size();
+    return 0;
+}
+
+extern "C" int mh_sam2aln_resident_rows(mh_ctx *ctx, int64_t first, int64_t n, int32_t *len,
+                                        uint8_t *seq, uint8_t *qual, size_t cap, size_t *used)
+{
+    if (!ctx || !used || first < 0 || n < 0) return -3;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    if (!c.s2a || c.s2a->staged_reads < 0 || c.s2a->staged_reads != c.reads.n) {
+        set_error("mh_sam2aln_resident_rows: no rows staged by mh_sam2aln_resident");
+        return -3;
+    }
+    if (first + n > c.reads.n) { set_error("mh_sam2aln_resident_rows: row range out of bounds"); return -3; }
+    const S2AState &S = *c.s2a;
+    std::vector<int64_t> off((size_t)n);
+    std::vector<int32_t> ln((size_t)n);
+    if (n > 0) {
+        MH_HIP(copy_sync(c, off.data(), c.reads.off + first, sizeof(int64_t) * (size_t)n,
+                         hipMemcpyDeviceToHost));
+        MH_HIP(copy_sync(c, ln.data(), c.reads.len + first, sizeof(int32_t) * (size_t)n,
+                         hipMemcpyDeviceToHost));
+    }
+    size_t total = 0;
+    for (int64_t k = 0; k < n; ++k) total += (size_t)ln[k];
+    *used = total;
+    if (!seq || !qual || !len) return 0;
+    if (cap < total) { set_error("mh_sam2aln_resident_rows: buffer too small"); return -2; }
+    if (n == 0) return 0;
+    const int64_t lo = off[0], hi = off[n - 1] + ln[n - 1];
+    std::vector<uint8_t> hs((size_t)(hi - lo) + 1), hq((size_t)(hi - lo) + 1);
+    if (hi > lo) {
+        MH_HIP(copy_sync(c, hs.data(), S.d_seq + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
+        MH_HIP(copy_sync(c, hq.data(), S.d_qual + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost));
+    }
+    size_t at = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        len[k] = ln[k];
+        memcpy(seq + at, hs.data() + (off[k] - lo), (size_t)ln[k]);
+        memcpy(qual + at, hq.data() + (off[k] - lo), (size_t)ln[k]);
+        at += (size_t)ln[k];
+    }
+    return 0;
 }
 
 extern "C" int mh_sam2aln_file_q(mh_ctx *ctx, int fd, int n_cut, const int32_t *q_cutoffs,

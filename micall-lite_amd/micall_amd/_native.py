@@ -125,6 +125,10 @@ def _declare(L):
         'mh_sam2aln_csv_q': ([_P, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_double,
                               _I64P], ctypes.c_int),
         'mh_sam2aln_file_q': ([_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_double, _I64P], ctypes.c_int),
+        'mh_sam2aln_resident': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, _P,
+                                 ctypes.c_double, _I64P], ctypes.c_int),
+        'mh_sam2aln_resident_rows': ([_P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_output': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
                                ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _I64P], ctypes.c_int),
@@ -369,6 +373,38 @@ class Context:
             return None
         check(st, 'mh_sam2aln_file')
         return n.value
+
+    def sam2aln_resident(self, refnames, q_cutoffs=(15,), max_prop_n=0.5):
+        """mh_sam2aln_resident: sam2aln over the records of the last map()
+        and the resident reads instead of the remap.csv written from them;
+        refnames = that pass's reference names.  The number of units, or
+        None when the rows of such a file would pair otherwise than the
+        reads do (parse the file)."""
+        cuts = np.ascontiguousarray(q_cutoffs, dtype=np.int32)
+        names = (ctypes.c_char_p * max(len(refnames), 1))(*[r.encode() for r in refnames])
+        n = ctypes.c_int64()
+        st = lib().mh_sam2aln_resident(self.h, len(refnames), names, len(cuts), _ptr(cuts),
+                                       float(max_prop_n), ctypes.byref(n))
+        if st == 1:
+            return None
+        check(st, 'mh_sam2aln_resident')
+        return n.value
+
+    def sam2aln_resident_rows(self, first=0, n=None):
+        """(lens, seq, qual) of rows [first, first + n) as the last
+        sam2aln_resident staged them on the device: int32 lengths and the
+        SEQ / QUAL bytes back to back (test entry point)."""
+        if n is None:
+            n = self.reads_count()[0] - first
+        used = ctypes.c_size_t()
+        check(lib().mh_sam2aln_resident_rows(self.h, first, n, None, None, None, 0, ctypes.byref(used)),
+              'mh_sam2aln_resident_rows')
+        lens = np.zeros(max(n, 1), dtype=np.int32)
+        seq = np.zeros(max(used.value, 1), dtype=np.uint8)
+        qual = np.zeros(max(used.value, 1), dtype=np.uint8)
+        check(lib().mh_sam2aln_resident_rows(self.h, first, n, _ptr(lens), _ptr(seq), _ptr(qual),
+                                             used.value, ctypes.byref(used)), 'mh_sam2aln_resident_rows')
+        return lens[:n], seq[:used.value].tobytes(), qual[:used.value].tobytes()
 
     # ---- sam2aln split over the ranks of a job (mh_s2a_shard.cpp) ----
     def sam2aln_part(self, fd, part, parts, q_cutoff=15, max_prop_n=0.5):

@@ -267,6 +267,7 @@ def remap(fastq1, fastq2, prelim_csv, remap_csv, remap_counts_csv=None, remap_co
                                                       remap_counts_writer=counts_out)
     if writer:
         csv.DictWriter(remap_csv, FIELDNAMES, lineterminator=os.linesep).writeheader()
+    run.rows_are_records = False
     # every rank writes its own rows / reads (sharded_io.SharedOutput)
     rows_out = sharded_io.SharedOutput(sh, remap_csv)
     unmapped_outs = [sharded_io.SharedOutput(sh, h) if h else None for h in (unmapped1, unmapped2)]
@@ -280,6 +281,14 @@ def remap(fastq1, fastq2, prelim_csv, remap_csv, remap_counts_csv=None, remap_co
     for out in [rows_out] + unmapped_outs:
         if out is not None:
             out.finish()
+    # sam2aln() may take remap.csv's rows from the device when the file holds
+    # every resident record once, in read order, and nothing else
+    if sh is None and new_counts and run.rows_are_records:
+        header = (','.join(FIELDNAMES) + os.linesep).encode()
+        session.remap_written(ctx, remap_csv, ctx.refnames,
+                              rows_out.crc_of_file(header) if rows_out.direct else None)
+    else:
+        session.remap_forget()
 
     if remap_conseq_csv and writer:
         # the sequences the reads were last mapped to (remap.py:637-643)
@@ -315,6 +324,8 @@ def _write_remap_rows(ctx, run, conseqs, new_counts, rows_out, unmapped_outs, sh
     keep_rows, splits = split_mixed_references(ctx)
     n_keep = ctx.reads_count()[0] if keep_rows is None else len(keep_rows)
     rows_out.write_rows(ctx, 1, keep_rows, [0, n_keep])
+    # no subset kept, no pair mapped again: the file is the records as they are
+    run.rows_are_records = keep_rows is None and not splits
     order = list(splits)
     if shard is not None:
         order = []

@@ -12,6 +12,13 @@ identical sequences run on the device (mh_sam2aln_csv, mh_sam2aln.hip); the
 host parses the CSV and writes the text.  nthreads is accepted for signature
 compatibility and ignored.  There is no CPU fallback.
 
+When remap_csv is the unchanged file this process's remap() just wrote from
+records that are still resident (session.remap_resident), nothing is parsed:
+the rows are built on the device from the resident reads and records
+(mh_sam2aln_resident) and the outputs are the same bytes.
+session.stats['sam2aln_source'] says which way a call went ('device' or
+'csv'); MICALL_SAM2ALN_RESIDENT=0 in the environment forces the file path.
+
 In a sharded job (torchrun) every rank takes its share of remap.csv's rows,
 merges its pairs on its GPU, and writes its own insert.csv / failed.csv rows
 and its piece of aligned.csv at all-gathered offsets; the distinct merged
@@ -21,6 +28,7 @@ parse_sam over pairs the same way (sam2aln.py:411-424).  The split takes one
 q-cutoff; with more, rank 0 does the whole stage.
 """
 import argparse
+import os
 
 import numpy as np
 
@@ -59,14 +67,21 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
+    session.stats['sam2aln_source'] = 'csv'
+    use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
     if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts):
         return
     with session.writer_stage(aligned_csv, insert_csv, failed_csv) as stage:
         if not stage.active:
             return
         ctx = session.context()
-        fd = session.readable_fd(remap_csv)
         done = None
+        if use_resident and session.remap_resident(ctx, remap_csv):
+            done = ctx.sam2aln_resident(session.remap_refnames(), q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
+            if done is not None:
+                remap_csv.seek(0, 2)     # consumed, as below
+                session.stats['sam2aln_source'] = 'device'
+        fd = session.readable_fd(remap_csv) if done is None else None
         if fd is not None:   # the file mmap'd by the library (no '\r' in it)
             done = ctx.sam2aln_file(fd, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
             if done is not None:

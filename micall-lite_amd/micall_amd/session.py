@@ -32,7 +32,10 @@ _key = None
 _shard = None
 _shard_checked = False
 _prelim = None     # what the last prelim_map() of this process wrote (prelim_written)
-stats = {}         # how the last calls ran (remap: 'prelim_source' = 'device' or 'csv')
+_remap = None      # what the last remap() of this process wrote (remap_written)
+# how the last calls ran: remap sets 'prelim_source', sam2aln 'sam2aln_source',
+# each to 'device' or 'csv'
+stats = {}
 
 
 def _device_index():
@@ -251,12 +254,8 @@ def _wait_past(ctime_ns, limit_s=0.05):
     return True
 
 
-def prelim_written(ctx, handle, seed_names, checksum=None):
-    """Record that prelim_map() wrote `handle` from the device records that
-    are resident now (ctx.map_serial) for these seeds: the file's identity
-    after the last write and, when known, (crc32, size) of its content as
-    formatted (no read-back)."""
-    global _prelim
+def _written(ctx, handle, checksum, **more):
+    """What prelim_written / remap_written keep of a file just written."""
     ident = None
     settled = False
     if is_writer():
@@ -266,8 +265,39 @@ def prelim_written(ctx, handle, seed_names, checksum=None):
             pass
         ident = _file_identity(handle)
         settled = ident is not None and _wait_past(ident[4])
-    _prelim = dict(identity=ident, settled=settled, checksum=checksum, serial=ctx.map_serial, key=_key,
-                   seeds=list(seed_names))
+    return dict(identity=ident, settled=settled, checksum=checksum, serial=ctx.map_serial, key=_key,
+                **more)
+
+
+def _unchanged_file(p, handle):
+    """`handle` is the file p records, unchanged and not read from yet: the
+    same identity or, failing that, the same size and crc32 (read back only
+    then), at offset 0."""
+    ident = _file_identity(handle)
+    ok = ident is not None and p['identity'] is not None
+    if ok and (ident != p['identity'] or not p['settled']):
+        ok = False
+        want = p['checksum']
+        if want is not None and ident[2] == want[1] and ident[:2] == p['identity'][:2]:
+            try:
+                ok = _native.file_crc32(handle.fileno()) == (want[1], want[0])
+            except (OSError, ValueError, _native.NativeError):
+                ok = False
+    if ok:
+        try:
+            ok = handle.tell() == 0
+        except (OSError, ValueError):
+            ok = False
+    return ok
+
+
+def prelim_written(ctx, handle, seed_names, checksum=None):
+    """Record that prelim_map() wrote `handle` from the device records that
+    are resident now (ctx.map_serial) for these seeds: the file's identity
+    after the last write and, when known, (crc32, size) of its content as
+    formatted (no read-back)."""
+    global _prelim
+    _prelim = _written(ctx, handle, checksum, seeds=list(seed_names))
 
 
 def prelim_resident(ctx, handle, seed_names):
@@ -282,39 +312,60 @@ def prelim_resident(ctx, handle, seed_names):
     ok = (p is not None and p['serial'] == ctx.map_serial and p['key'] == _key and
           p['key'] is not None and p['seeds'] == list(seed_names))
     if ok and is_writer():
-        ident = _file_identity(handle)
-        ok = ident is not None and p['identity'] is not None
-        if ok and (ident != p['identity'] or not p['settled']):
-            ok = False
-            want = p['checksum']
-            if want is not None and ident[2] == want[1] and ident[:2] == p['identity'][:2]:
-                try:
-                    ok = _native.file_crc32(handle.fileno()) == (want[1], want[0])
-                except (OSError, ValueError, _native.NativeError):
-                    ok = False
-        if ok:
-            try:
-                ok = handle.tell() == 0
-            except (OSError, ValueError):
-                ok = False
+        ok = _unchanged_file(p, handle)
     sh = shard()
     if sh is not None:
         ok = bool(sh.min_i64([1 if ok else 0])[0])
     return ok
 
 
+def remap_written(ctx, handle, refnames, checksum=None):
+    """Record that remap() wrote `handle` from the device records that are
+    resident now (ctx.map_serial): every resident read once, in read order,
+    mapped to `refnames`.  Kept like prelim_written keeps prelim.csv: the
+    file's identity after the last write and, when known, (crc32, size) of
+    its content as formatted."""
+    global _remap
+    _remap = _written(ctx, handle, checksum, refnames=list(refnames))
+
+
+def remap_forget():
+    """remap.csv is not (only) the resident records: sam2aln() parses it."""
+    global _remap
+    _remap = None
+
+
+def remap_resident(ctx, handle):
+    """True when `handle` is the remap.csv this process's last remap() wrote
+    from the records still resident, unchanged (as prelim_resident tests
+    prelim.csv), not read from yet and readable by the native parser:
+    sam2aln() then takes the rows from the device (remap_refnames() names
+    their references) instead of parsing the file."""
+    p = _remap
+    return (p is not None and p['serial'] == ctx.map_serial and p['key'] == _key and
+            p['key'] is not None and shard() is None and _unchanged_file(p, handle) and
+            readable_fd(handle) is not None)
+
+
+def remap_refnames():
+    """The reference names of the pass remap_written recorded."""
+    return list(_remap['refnames'])
+
+
 def invalidate():
     """The resident reads were replaced (e.g. by split re-mapping)."""
-    global _key, _prelim
+    global _key, _prelim, _remap
     _key = None
     _prelim = None
+    _remap = None
 
 
 def reset():
     """Close the process-wide context (the next call creates a new one)."""
-    global _ctx, _key, _prelim
+    global _ctx, _key, _prelim, _remap
     if _ctx is not None:
         _ctx.close()
     _ctx = None
     _key = None
     _prelim = None
+    _remap = None
