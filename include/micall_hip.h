@@ -416,6 +416,15 @@ int mh_sam2aln_resident_rows(mh_ctx *ctx, int64_t first, int64_t n, int32_t *len
  * Not sized before (no mh_sam2aln_output size query), it is formatted and
  * written in one pass, the writes overlapping the formatting. */
 int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *written);
+/* What the last mh_sam2aln_write of aligned.csv (which 0, the only one kept)
+ * wrote: the crc32 of its text, joined from the formatted pieces' own
+ * (nothing is read back), and its size.  -3 when this context's sam2aln
+ * results were not written that way since they were computed. */
+int mh_sam2aln_written(mh_ctx *ctx, int which, uint32_t *crc, int64_t *bytes);
+/* The number of calls that have rebuilt the context's sam2aln results so far
+ * (mh_sam2aln_csv[_q], _file[_q], _resident, _part): equal serials mean the
+ * results are those of the same call. */
+int mh_sam2aln_serial(mh_ctx *ctx, int64_t *serial);
 /* Of the last call of either kind: out[0] pairs, out[1] pairs merged on the
  * device, out[2] distinct (rname, q-cutoff, merged sequence), i.e. the data
  * rows of aligned.csv, out[3] failed pairs, i.e. the data rows of failed.csv. */
@@ -537,6 +546,18 @@ int mh_a2c_load_csv(mh_ctx *ctx, int slot, const char *text, int64_t len,
 /* mh_a2c_load_csv on the whole of a regular file (fd, mmap'd): 0, or 1 when
  * the file holds '\r' (the caller reads it in text mode instead). */
 int mh_a2c_load_file(mh_ctx *ctx, int slot, int fd, const char *codon_chars, int64_t *n_groups);
+/* The same table as mh_a2c_load_file on the aligned.csv of this context's
+ * last sam2aln call, built on the device from that call's resident results
+ * (nothing is formatted or parsed): the rows in aligned.csv's order
+ * (k_a2c_stage), the bin lists (k_a2c_bin_count / k_a2c_bin_fill), then
+ * k_a2c_count as for a file; the sequence bytes are copied into the slot, so
+ * a later sam2aln call leaves it intact.  0, or 1 when the rows cannot stand
+ * for the file and the caller loads the file instead: no complete un-sharded
+ * sam2aln result in the context; a reference name holding '"', ',', '\r' or
+ * '\n'; 2^31-1 rows or more, a group whose counts add up to more than 2^32-1,
+ * an offset or length above 2^28; a sequence byte outside A C G T N - n.
+ * Negative only for HIP / allocation failures. */
+int mh_a2c_load_resident(mh_ctx *ctx, int slot, const char *codon_chars, int64_t *n_groups);
 /* The same from rows in memory: row r's seq is pool[seq_off[r] ..
  * seq_off[r] + seq_len[r]); group g = rows group_first[g] ..
  * group_first[g + 1] - 1 (group names are empty). */
@@ -570,7 +591,9 @@ int mh_a2c_insert_entries(mh_ctx *ctx, int slot, int32_t *range, int64_t *count,
 int mh_a2c_insert_rows(mh_ctx *ctx, int slot, const char *lead, int n_ranges, const int32_t *left,
                        const int32_t *target, const char *eol, char *buf, size_t cap, size_t *used);
 /* Host wall ms: [0] parse of the last load, [1] its upload + k_a2c_count +
- * fetch, [2] mh_a2c_inserts since the last call of this function. */
+ * fetch, [2] mh_a2c_inserts since the last call of this function.  After
+ * mh_a2c_load_resident: [0] the row order (when not built yet) + staging
+ * (k_a2c_stage), [1] the bin lists + k_a2c_count + fetch. */
 int mh_a2c_timing(mh_ctx *ctx, int slot, double *ms3);
 
 /* ---- aln2counts counting split over the ranks of a job (the same

@@ -18,6 +18,10 @@
 //                 Counter insertion order that most_common() breaks ties by
 //                 (:624, :668).  One global atomic per touched counter
 //                 flushes the chunk.
+//   k_a2c_stage, k_a2c_bin_count / _scan / _fill
+//                 the rows and the bin lists built on the device from the
+//                 results sam2aln left there (mh_a2c_load_resident): what the
+//                 host half below builds from the text of aligned.csv.
 //   k_a2c_ins_*   the read loop of InsertionWriter.write (:786-795): per
 //                 (insert range, row) the framed slice [3 left, 3 right) of
 //                 the read, rejected when it starts in the padding, holds '-'
@@ -31,6 +35,7 @@
 // codon extent of every frame, the bin lists.
 // Bit-for-bit specification: oracle/og_aln2counts.py.
 #include <algorithm>
+#include <atomic>
 #include <charconv>
 #include <chrono>
 #include <cstring>
@@ -102,6 +107,11 @@ struct A2CState {
     int32_t *d_bin_rows = nullptr;
     A2CChunk *d_chunks = nullptr;
     uint32_t *d_cnt = nullptr, *d_first = nullptr;
+    // mh_a2c_load_resident: the rows were built on the device (rows is
+    // empty; every group's first row has local 0) from these uploads
+    bool dev_rows = false;
+    int32_t *d_order = nullptr, *d_gfirst = nullptr, *d_gbin0 = nullptr, *d_ncod = nullptr;
+    unsigned long long *d_bstart = nullptr, *d_bcur = nullptr;
     // insertion strings of the last mh_a2c_inserts, in (range, first row) order
     std::vector<A2CEntry> entries;
     std::string aminos;                       // one line per entry
@@ -181,6 +191,207 @@ __global__ __launch_bounds__(256) void k_a2c_count(A2CCountArgs A)
         if (fr == A2C_NONE) continue;
         if (s_cnt[i]) atomicAdd(&A.cnt[base + i], s_cnt[i]);
         atomicMin(&A.first[base + i], fr);
+    }
+}
+
+// The bins of its group a row reaches: every codon of every frame it touches
+// (frame 2 reaches furthest) lies in bins b0 .. b1.
+__host__ __device__ inline void a2c_row_bins(int off, int len, int &b0, int &b1)
+{
+    b0 = (off / 3) / A2C_W;
+    b1 = ((2 + off + len + 2) / 3 - 1) / A2C_W;
+}
+
+// ---- rows and bin lists from sam2aln's resident results -------------------
+constexpr int A2C_TEAM = 16;            // lanes sharing one row's bytes (16 B each per load)
+constexpr int A2C_STAGE_GROUPS = 64;    // groups of one block's rows reduced in LDS
+constexpr int A2C_LDS_BINS = 1024;      // bins of one block's rows counted in LDS
+
+struct A2CStageArgs {
+    const int32_t *order;    // per row of aligned.csv: k of uniq
+    const int32_t *gfirst;   // n_groups + 1: first row of each group
+    const int64_t *goff;     // per k: where its body starts in text
+    const int32_t *res;      // per merge entry: status, offset, body length, stripped length
+    const int32_t *uniq;     // per k: representative entry, count
+    const uint8_t *text;     // the slot's copy of the bodies (16 spare bytes behind them)
+    const uint8_t *cls;
+    A2CRow *rows;
+    int32_t *ncod;           // 3 per group (zeroed), then one word: a byte of class A2C_BAD seen
+    int32_t n_rows, n_groups, per_block;
+};
+
+// the group g with gfirst[g] <= i < gfirst[g + 1] (no group is empty)
+__device__ __forceinline__ int a2c_group_of(const int32_t *gfirst, int n_groups, int64_t i)
+{
+    int lo = 0, hi = n_groups;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (gfirst[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Row i of aligned.csv as a2c_row reads it from the text: its A2CRow, its
+// bytes tested against cls, its codons added to its group's extent per frame
+// (a2c_layout).  A block takes per_block consecutive rows, a team of 16
+// lanes a row: each lane tests 16 bytes of one aligned load, so a row of a
+// few hundred bytes is one or two loads of the team.  The extents of the
+// block's first A2C_STAGE_GROUPS groups are reduced in LDS and leave the
+// block as one atomicMax per group and frame.
+__global__ __launch_bounds__(256) void k_a2c_stage(A2CStageArgs A)
+{
+    __shared__ uint8_t s_cls[256];
+    __shared__ int s_hi[3 * A2C_STAGE_GROUPS];
+    __shared__ int s_g0;
+    const int64_t r0 = (int64_t)blockIdx.x * A.per_block;
+    const int64_t r1 = r0 + A.per_block < A.n_rows ? r0 + A.per_block : A.n_rows;
+    s_cls[threadIdx.x] = A.cls[threadIdx.x];
+    if (threadIdx.x < 3 * A2C_STAGE_GROUPS) s_hi[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_g0 = a2c_group_of(A.gfirst, A.n_groups, r0);
+    __syncthreads();
+    const int team = threadIdx.x / A2C_TEAM, tl = threadIdx.x % A2C_TEAM;
+    int g = s_g0;
+    bool bad = false;
+    for (int64_t i = r0 + team; i < r1; i += 256 / A2C_TEAM) {
+        while (i >= A.gfirst[g + 1]) ++g;
+        const int k = A.order[i];
+        const int rep = A.uniq[2 * k];
+        A2CRow R;
+        R.soff = A.goff[k];
+        R.len = A.res[4 * (int64_t)rep + 3];
+        R.off = A.res[4 * (int64_t)rep + 1];
+        R.cnt = (uint32_t)A.uniq[2 * k + 1];
+        R.local = (uint32_t)(i - A.gfirst[g]);
+        if (tl == 0) {
+            A.rows[i] = R;
+            const int lo = R.off / 3, gl = g - s_g0;
+            for (int f = 0; f < 3; ++f) {
+                const int hi = (f + R.off + R.len + 2) / 3;
+                if (hi <= lo) continue;
+                if (gl < A2C_STAGE_GROUPS) atomicMax(&s_hi[3 * gl + f], hi);
+                else atomicMax(&A.ncod[3 * g + f], hi);
+            }
+        }
+        const int64_t b = R.soff, e = R.soff + R.len;
+        for (int64_t p = (b & ~(int64_t)15) + 16 * tl; p < e; p += 16 * A2C_TEAM) {
+            const uint4 w = *reinterpret_cast<const uint4 *>(A.text + p);
+            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const uint32_t ch = (ww[q >> 2] >> (8 * (q & 3))) & 0xffu;
+                if (p + q >= b && p + q < e && s_cls[ch] == A2C_BAD) bad = true;
+            }
+        }
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&A.ncod[3 * A.n_groups], 1);
+    __syncthreads();
+    if (threadIdx.x < 3 * A2C_STAGE_GROUPS && s_hi[threadIdx.x] > 0)
+        atomicMax(&A.ncod[3 * (s_g0 + threadIdx.x / 3) + threadIdx.x % 3], s_hi[threadIdx.x]);
+}
+
+struct A2CBinArgs {
+    const A2CRow *rows;
+    const int32_t *gfirst, *gbin0;    // n_groups + 1 each: first row, first bin of each group
+    int32_t n_rows, n_groups;
+    unsigned long long *cnt;          // k_a2c_bin_count: rows per bin (zeroed)
+    unsigned long long *cur;          // k_a2c_bin_fill: the next free place of each bin's list
+    int32_t *bin_rows;
+    unsigned long long total;         // places in bin_rows
+};
+
+// the bins [b0, b1] (numbered over all groups) of row i, the empty range
+// past the last row; g0 = the first bin of the group of the block's first row
+__device__ __forceinline__ void a2c_bins_of(const A2CBinArgs &A, int64_t i, int &b0, int &b1, int *g0)
+{
+    b0 = 0;
+    b1 = -1;
+    if (i >= A.n_rows) return;
+    const int g = a2c_group_of(A.gfirst, A.n_groups, i);
+    const A2CRow R = A.rows[i];
+    a2c_row_bins(R.off, R.len, b0, b1);
+    b0 += A.gbin0[g];
+    b1 += A.gbin0[g];
+    if (b1 >= A.gbin0[g + 1]) b1 = A.gbin0[g + 1] - 1;   // (its group's extent covers the row)
+    if (g0) *g0 = A.gbin0[g];
+}
+
+// Rows per bin.  A million rows of one group share some fifty bins, and
+// atomics on one global address serialise, so a block of 256 consecutive
+// rows counts into an LDS table of the A2C_LDS_BINS bins from its first
+// row's group on (1024 bins = 21 504 codons: several groups of a block, or
+// one 64 kb reference) and adds each touched bin to the global count once;
+// bins past the table are counted in global memory directly.
+__global__ __launch_bounds__(256) void k_a2c_bin_count(A2CBinArgs A)
+{
+    __shared__ uint32_t s_n[A2C_LDS_BINS];
+    __shared__ int s_b0;
+    for (int k = threadIdx.x; k < A2C_LDS_BINS; k += 256) s_n[k] = 0;
+    int b0, b1;
+    a2c_bins_of(A, (int64_t)blockIdx.x * 256 + threadIdx.x, b0, b1, threadIdx.x == 0 ? &s_b0 : nullptr);
+    __syncthreads();
+    for (int b = b0; b <= b1; ++b) {
+        if (b - s_b0 < A2C_LDS_BINS) atomicAdd(&s_n[b - s_b0], 1u);
+        else atomicAdd(&A.cnt[b], 1ull);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < A2C_LDS_BINS; k += 256)
+        if (s_n[k]) atomicAdd(&A.cnt[s_b0 + k], (unsigned long long)s_n[k]);
+}
+
+// start[b] = cnt[0] + .. + cnt[b - 1] for b = 0 .. n (one block)
+__global__ __launch_bounds__(1024) void k_a2c_bin_scan(const unsigned long long *cnt,
+                                                       unsigned long long *start, int n)
+{
+    __shared__ unsigned long long s[1024];
+    const int per = (n + 1023) / 1024;
+    const int64_t a0 = (int64_t)threadIdx.x * per;
+    const int a = a0 < n ? (int)a0 : n, b = a0 + per < n ? (int)(a0 + per) : n;
+    unsigned long long sum = 0;
+    for (int i = a; i < b; ++i) sum += cnt[i];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const unsigned long long v = (int)threadIdx.x >= d ? s[threadIdx.x - d] : 0;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned long long run = s[threadIdx.x] - sum;
+    for (int i = a; i < b; ++i) {
+        start[i] = run;
+        run += cnt[i];
+    }
+    if (threadIdx.x == 1023) start[n] = s[1023];
+}
+
+// The bin lists: the block counts as k_a2c_bin_count does, takes its range
+// of every touched bin's list with one global atomicAdd, and its rows take
+// their places inside the ranges through the LDS counts.  The order of the
+// rows of a bin is free (k_a2c_count adds counts and takes the least row).
+__global__ __launch_bounds__(256) void k_a2c_bin_fill(A2CBinArgs A)
+{
+    __shared__ uint32_t s_n[A2C_LDS_BINS];
+    __shared__ unsigned long long s_at[A2C_LDS_BINS];
+    __shared__ int s_b0;
+    for (int k = threadIdx.x; k < A2C_LDS_BINS; k += 256) s_n[k] = 0;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int b0, b1;
+    a2c_bins_of(A, i, b0, b1, threadIdx.x == 0 ? &s_b0 : nullptr);
+    __syncthreads();
+    for (int b = b0; b <= b1; ++b)
+        if (b - s_b0 < A2C_LDS_BINS) atomicAdd(&s_n[b - s_b0], 1u);
+    __syncthreads();
+    for (int k = threadIdx.x; k < A2C_LDS_BINS; k += 256)
+        if (s_n[k]) {
+            s_at[k] = atomicAdd(&A.cur[s_b0 + k], (unsigned long long)s_n[k]);
+            s_n[k] = 0;
+        }
+    __syncthreads();
+    for (int b = b0; b <= b1; ++b) {
+        const unsigned long long at = b - s_b0 < A2C_LDS_BINS
+                                          ? s_at[b - s_b0] + atomicAdd(&s_n[b - s_b0], 1u)
+                                          : atomicAdd(&A.cur[b], 1ull);
+        if (at < A.total) A.bin_rows[at] = (int32_t)i;
     }
 }
 
@@ -340,6 +551,10 @@ static void a2c_free_device(A2CState &S)
 {
     hipFree(S.d_text); hipFree(S.d_cls); hipFree(S.d_code); hipFree(S.d_rows);
     hipFree(S.d_bin_rows); hipFree(S.d_chunks); hipFree(S.d_cnt); hipFree(S.d_first);
+    hipFree(S.d_order); hipFree(S.d_gfirst); hipFree(S.d_gbin0); hipFree(S.d_ncod);
+    hipFree(S.d_bstart); hipFree(S.d_bcur);
+    S.d_order = S.d_gfirst = S.d_gbin0 = S.d_ncod = nullptr;
+    S.d_bstart = S.d_bcur = nullptr;
     S.d_text = S.d_cls = nullptr;
     S.d_code = nullptr;
     S.d_rows = nullptr;
@@ -544,9 +759,9 @@ static int a2c_layout(A2CState &S, std::vector<int32_t> &bin_rows, std::vector<A
     for (int64_t g = 0; g < ng; ++g)
         for (int64_t r = S.g_first[g]; r < S.g_first[g + 1]; ++r) {
             const A2CRow &R = S.rows[r];
-            const int64_t b0 = S.g_bin0[g] + (R.off / 3) / A2C_W;
-            const int64_t b1 = S.g_bin0[g] + ((2 + R.off + R.len + 2) / 3 - 1) / A2C_W;
-            for (int64_t b = b0; b <= b1; ++b) ++start[b + 1];
+            int r0, r1;
+            a2c_row_bins(R.off, R.len, r0, r1);
+            for (int64_t b = S.g_bin0[g] + r0; b <= S.g_bin0[g] + r1; ++b) ++start[b + 1];
         }
     for (int64_t b = 0; b < S.n_bins; ++b) start[b + 1] += start[b];
     bin_rows.assign(start[S.n_bins], 0);
@@ -554,9 +769,9 @@ static int a2c_layout(A2CState &S, std::vector<int32_t> &bin_rows, std::vector<A
     for (int64_t g = 0; g < ng; ++g)
         for (int64_t r = S.g_first[g]; r < S.g_first[g + 1]; ++r) {
             const A2CRow &R = S.rows[r];
-            const int64_t b0 = S.g_bin0[g] + (R.off / 3) / A2C_W;
-            const int64_t b1 = S.g_bin0[g] + ((2 + R.off + R.len + 2) / 3 - 1) / A2C_W;
-            for (int64_t b = b0; b <= b1; ++b) bin_rows[cur[b]++] = (int32_t)r;
+            int r0, r1;
+            a2c_row_bins(R.off, R.len, r0, r1);
+            for (int64_t b = S.g_bin0[g] + r0; b <= S.g_bin0[g] + r1; ++b) bin_rows[cur[b]++] = (int32_t)r;
         }
     chunks.clear();
     for (int64_t g = 0; g < ng; ++g)
@@ -589,6 +804,8 @@ static int a2c_upload(A2CState &S, T *&dst, const T *src, size_t n, hipStream_t 
     return 0;
 }
 
+static int a2c_count_chunks(Ctx &c, A2CState &S, size_t n_chunks);
+
 // upload the rows, count every group on the device, fetch the counters
 static int a2c_count(Ctx &c, A2CState &S, const char *text, int64_t text_len, bool preset = false)
 {
@@ -602,6 +819,14 @@ static int a2c_count(Ctx &c, A2CState &S, const char *text, int64_t text_len, bo
     if (int st = a2c_upload(S, S.d_chunks, chunks.data(), chunks.size(), s)) return st;
     if (int st = a2c_upload(S, S.d_code, S.code, 512, s)) return st;
     if (int st = a2c_upload(S, S.d_cls, S.cls, 256, s)) return st;
+    return a2c_count_chunks(c, S, chunks.size());
+}
+
+// k_a2c_count over the n_chunks chunks on the device (rows, bin lists, text
+// and tables are there), the counters fetched
+static int a2c_count_chunks(Ctx &c, A2CState &S, size_t n_chunks)
+{
+    hipStream_t s = c.stream;
     const size_t cells = (size_t)S.n_bins * A2C_CELLS;
     if (int st = a2c_reserve(S, S.d_cnt, sizeof(uint32_t) * cells)) return st;
     if (int st = a2c_reserve(S, S.d_first, sizeof(uint32_t) * cells)) return st;
@@ -609,11 +834,11 @@ static int a2c_count(Ctx &c, A2CState &S, const char *text, int64_t text_len, bo
         MH_HIP(hipMemsetAsync(S.d_cnt, 0, sizeof(uint32_t) * cells, s));
         MH_HIP(hipMemsetAsync(S.d_first, 0xff, sizeof(uint32_t) * cells, s));
     }
-    if (!chunks.empty()) {
+    if (n_chunks) {
         A2CCountArgs a{S.d_text, S.d_rows, S.d_bin_rows, S.d_chunks, S.d_code, S.d_cls,
                        S.d_cnt, S.d_first};
         const int p0 = prof_begin(c, "k_a2c_count");
-        hipLaunchKernelGGL(k_a2c_count, dim3((unsigned)chunks.size()), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_a2c_count, dim3((unsigned)n_chunks), dim3(256), 0, s, a);
         prof_end(c, p0);
         MH_HIP(hipGetLastError());
     }
@@ -636,6 +861,7 @@ static int a2c_parse_csv(A2CState &S, const char *text, int64_t len, bool &use_p
     const char *p = text, *end = text + len;
     std::vector<std::string> head;
     S.rows.clear();
+    S.dev_rows = false;
     S.g_first.assign(1, 0);
     S.g_ref.clear();
     S.g_qcut.clear();
@@ -804,6 +1030,185 @@ extern "C" int mh_a2c_load_file(mh_ctx *ctx, int slot, int fd, const char *codon
     return rc;
 }
 
+// The rows of aligned.csv from the results sam2aln left on the device: see
+// micall_hip.h.  1: the caller loads the file (whose errors are then the
+// file path's own).
+static int a2c_load_resident(Ctx &c, A2CState &S, int64_t *n_groups)
+{
+    if (!c.s2a || !c.s2a->complete) return 1;
+    S2AState &Q = *c.s2a;
+    auto t0 = std::chrono::steady_clock::now();
+    s2a_order(Q);
+    const S2AOrder &O = Q.order;
+    const int64_t ng = (int64_t)O.g_name.size(), n = O.g_first.back();
+    const int64_t ne = Q.n_merge * (int64_t)Q.q_cutoffs.size();
+    const int64_t text_len = Q.n_unique ? Q.uniq_off[(size_t)Q.n_unique] : 0;
+    if (n >= INT32_MAX) return 1;
+    if (n && (!Q.d_gather || !Q.d_goff || !Q.d_res || !Q.d_uniq || text_len <= 0)) return 1;
+    for (int64_t g = 0; g < ng; ++g) {
+        const std::string &name = Q.names[(size_t)O.g_name[g]];
+        if (name.find_first_of("\",\r\n") != std::string::npos) return 1;
+        if (O.g_total[g] > UINT32_MAX) return 1;
+        // two runs of one (refname, qcut) side by side are one group of the file
+        if (g && O.g_qcut[g] == O.g_qcut[g - 1] && name == Q.names[(size_t)O.g_name[g - 1]]) return 1;
+    }
+    // the limits a2c_row checks, and every index the kernels follow
+    const int nt = std::max(1, std::min(s2a_threads(), (int)(n >> 16) + 1));
+    std::atomic<int> off_limits(0), broken(0);
+    par_for(nt, [&](int t) {
+        for (int64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) {
+            const int64_t k = O.rows[(size_t)i];
+            if (k < 0 || k >= Q.n_unique) { broken = 1; return; }
+            const int64_t rep = Q.uniq[2 * k];
+            if (rep < 0 || rep >= ne) { broken = 1; return; }
+            const int64_t off = Q.res[4 * rep + 1], len = Q.res[4 * rep + 3];
+            if (len < 0 || len > Q.uniq_off[(size_t)k + 1] - Q.uniq_off[(size_t)k] || Q.uniq[2 * k + 1] < 0) {
+                broken = 1;
+                return;
+            }
+            if (off < 0 || off > A2C_MAX_SPAN || len > A2C_MAX_SPAN) { off_limits = 1; return; }
+        }
+    });
+    if (broken) {
+        set_error("mh_a2c_load_resident: the sam2aln results are inconsistent");
+        return -3;
+    }
+    if (off_limits) return 1;
+    S.rows.clear();
+    S.dev_rows = true;
+    S.n_rows = n;
+    S.pool.clear();
+    S.g_first = O.g_first;
+    S.g_ref.clear();
+    S.g_qcut.clear();
+    for (int64_t g = 0; g < ng; ++g) {
+        S.g_ref.push_back(Q.names[(size_t)O.g_name[g]]);
+        S.g_qcut.push_back(std::to_string(O.g_qcut[g]));
+    }
+    S.g_ncod.assign(3 * (size_t)ng, 0);
+    S.g_bin0.assign((size_t)ng + 1, 0);
+    S.n_bins = 0;
+    hipStream_t s = c.stream;
+    if (int st = a2c_upload(S, S.d_code, S.code, 512, s)) return st;
+    if (int st = a2c_upload(S, S.d_cls, S.cls, 256, s)) return st;
+    size_t n_chunks = 0;
+    auto t1 = t0;
+    if (n) {
+        // ---- staging: the bodies into the slot, the rows, the codon extents ----
+        std::vector<int32_t> gfirst(O.g_first.begin(), O.g_first.end());
+        if (int st = a2c_upload(S, S.d_order, O.rows.data(), (size_t)n, s)) return st;
+        if (int st = a2c_upload(S, S.d_gfirst, gfirst.data(), gfirst.size(), s)) return st;
+        if (int st = a2c_reserve(S, S.d_text, (size_t)text_len + 16)) return st;
+        if (int st = a2c_reserve(S, S.d_rows, sizeof(A2CRow) * (size_t)n)) return st;
+        if (int st = a2c_reserve(S, S.d_ncod, sizeof(int32_t) * (3 * (size_t)ng + 1))) return st;
+        MH_HIP(hipMemcpyAsync(S.d_text, Q.d_gather, (size_t)text_len, hipMemcpyDeviceToDevice, s));
+        MH_HIP(hipMemsetAsync(S.d_text + text_len, 0, 16, s));
+        MH_HIP(hipMemsetAsync(S.d_ncod, 0, sizeof(int32_t) * (3 * (size_t)ng + 1), s));
+        int64_t per_block = (n + 2047) / 2048;
+        per_block = std::max<int64_t>(256 / A2C_TEAM, (per_block + 15) & ~(int64_t)15);
+        A2CStageArgs a{S.d_order, S.d_gfirst, Q.d_goff, Q.d_res, Q.d_uniq, S.d_text, S.d_cls, S.d_rows,
+                       S.d_ncod, (int32_t)n, (int32_t)ng, (int32_t)per_block};
+        const int p0 = prof_begin(c, "k_a2c_stage");
+        hipLaunchKernelGGL(k_a2c_stage, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), 0, s, a);
+        prof_end(c, p0);
+        MH_HIP(hipGetLastError());
+        std::vector<int32_t> ncod(3 * (size_t)ng + 1);
+        MH_HIP(hipMemcpyAsync(ncod.data(), S.d_ncod, sizeof(int32_t) * ncod.size(), hipMemcpyDeviceToHost, s));
+        MH_HIP(hipStreamSynchronize(s));
+        prof_flush(c);
+        if (ncod[3 * (size_t)ng]) return 1;     // a byte the file path names in its error
+        S.t_parse = ms_since(t0);
+        t1 = std::chrono::steady_clock::now();
+        // ---- layout: bins per group, rows per bin, the bin lists, the chunks ----
+        std::vector<int32_t> gbin0((size_t)ng + 1, 0);
+        for (int64_t g = 0; g < ng; ++g) {
+            const int32_t *nc = &ncod[3 * (size_t)g];
+            for (int f = 0; f < 3; ++f) S.g_ncod[3 * (size_t)g + f] = nc[f];
+            const int top = std::max(nc[0], std::max(nc[1], nc[2]));
+            S.g_bin0[(size_t)g + 1] = S.g_bin0[(size_t)g] + (top + A2C_W - 1) / A2C_W;
+            if (S.g_bin0[(size_t)g + 1] >= INT32_MAX) return 1;
+            gbin0[(size_t)g + 1] = (int32_t)S.g_bin0[(size_t)g + 1];
+        }
+        S.n_bins = S.g_bin0[(size_t)ng];
+        const size_t nb = (size_t)S.n_bins;
+        if (int st = a2c_upload(S, S.d_gbin0, gbin0.data(), gbin0.size(), s)) return st;
+        if (int st = a2c_reserve(S, S.d_bstart, sizeof(unsigned long long) * (nb + 1))) return st;
+        if (int st = a2c_reserve(S, S.d_bcur, sizeof(unsigned long long) * (nb + 1))) return st;
+        MH_HIP(hipMemsetAsync(S.d_bcur, 0, sizeof(unsigned long long) * (nb + 1), s));
+        A2CBinArgs b{S.d_rows, S.d_gfirst, S.d_gbin0, (int32_t)n, (int32_t)ng, S.d_bcur, nullptr, nullptr, 0};
+        const unsigned row_blocks = (unsigned)((n + 255) / 256);
+        const int p1 = prof_begin(c, "k_a2c_bin_count");
+        hipLaunchKernelGGL(k_a2c_bin_count, dim3(row_blocks), dim3(256), 0, s, b);
+        prof_end(c, p1);
+        const int p2 = prof_begin(c, "k_a2c_bin_scan");
+        hipLaunchKernelGGL(k_a2c_bin_scan, dim3(1), dim3(1024), 0, s, S.d_bcur, S.d_bstart, (int)nb);
+        prof_end(c, p2);
+        MH_HIP(hipGetLastError());
+        std::vector<unsigned long long> start(nb + 1);
+        MH_HIP(hipMemcpyAsync(start.data(), S.d_bstart, sizeof(unsigned long long) * (nb + 1),
+                              hipMemcpyDeviceToHost, s));
+        // the lists are filled from copies of the starts
+        MH_HIP(hipMemcpyAsync(S.d_bcur, S.d_bstart, sizeof(unsigned long long) * (nb + 1),
+                              hipMemcpyDeviceToDevice, s));
+        MH_HIP(hipStreamSynchronize(s));
+        std::vector<A2CChunk> chunks;
+        for (int64_t g = 0; g < ng; ++g)
+            for (int64_t bin = S.g_bin0[(size_t)g]; bin < S.g_bin0[(size_t)g + 1]; ++bin)
+                for (int64_t i = (int64_t)start[(size_t)bin]; i < (int64_t)start[(size_t)bin + 1]; i += A2C_CHUNK)
+                    chunks.push_back({(int32_t)bin, (int32_t)((bin - S.g_bin0[(size_t)g]) * A2C_W), i,
+                                      std::min<int64_t>(i + A2C_CHUNK, (int64_t)start[(size_t)bin + 1])});
+        n_chunks = chunks.size();
+        if (int st = a2c_reserve(S, S.d_bin_rows, sizeof(int32_t) * (size_t)start[nb])) return st;
+        if (int st = a2c_upload(S, S.d_chunks, chunks.data(), chunks.size(), s)) return st;
+        b.cnt = nullptr;
+        b.cur = S.d_bcur;
+        b.bin_rows = S.d_bin_rows;
+        b.total = start[nb];
+        const int p3 = prof_begin(c, "k_a2c_bin_fill");
+        hipLaunchKernelGGL(k_a2c_bin_fill, dim3(row_blocks), dim3(256), 0, s, b);
+        prof_end(c, p3);
+        MH_HIP(hipGetLastError());
+    } else {
+        S.t_parse = ms_since(t0);
+        t1 = std::chrono::steady_clock::now();
+    }
+    if (int st = a2c_count_chunks(c, S, n_chunks)) return st;
+    S.t_count = ms_since(t1);
+    if (n_groups) *n_groups = ng;
+    return 0;
+}
+
+extern "C" int mh_a2c_load_resident(mh_ctx *ctx, int slot, const char *codon_chars, int64_t *n_groups)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS) return -3;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    A2CState &S = *a2c_state(c, slot);
+    a2c_clear_inserts(S);
+    if (S.part_text) {       // a part left open by a sharded load that fell back
+        unmap_text_file(S.part_text, S.part_len);
+        S.part_text = nullptr;
+        S.part_open = false;
+    }
+    if (int st = a2c_tables(S, codon_chars)) return st;
+    int st = 0;
+    try {
+        st = a2c_load_resident(c, S, n_groups);
+    } catch (const std::exception &e) {
+        set_error("mh_a2c_load_resident: out of memory (%s)", e.what());
+        st = -2;
+    }
+    if (st) {                // nothing of a load that did not finish stands
+        S.rows.clear();
+        S.dev_rows = false;
+        S.n_rows = 0;
+        S.g_first.assign(1, 0);
+        S.g_ref.clear();
+        S.g_qcut.clear();
+    }
+    return st;
+}
+
 extern "C" int mh_a2c_load_rows(mh_ctx *ctx, int slot, int64_t n_rows, const char *pool,
                                 int64_t pool_len, const int64_t *seq_off, const int32_t *seq_len,
                                 const int64_t *offset, const int64_t *count, int64_t n_groups,
@@ -823,6 +1228,7 @@ extern "C" int mh_a2c_load_rows(mh_ctx *ctx, int slot, int64_t n_rows, const cha
         return -3;
     }
     S.rows.assign(n_rows, A2CRow{});
+    S.dev_rows = false;
     for (int64_t r = 0; r < n_rows; ++r) {
         if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > pool_len ||
             seq_len[r] > A2C_MAX_SPAN) {
@@ -961,7 +1367,7 @@ extern "C" int mh_a2c_inserts(mh_ctx *ctx, int slot, int64_t g, int frame, int n
     if (e != hipSuccess) { fail(e, "mh_a2c_inserts alloc"); goto done; }
     a.text = S.d_text;
     a.rows = S.d_rows + S.g_first[g];
-    a.row0 = S.rows[(size_t)S.g_first[g]].local;
+    a.row0 = S.dev_rows ? 0 : S.rows[(size_t)S.g_first[g]].local;
     a.code = S.d_code;
     a.cls = S.d_cls;
     a.left = d_lr;

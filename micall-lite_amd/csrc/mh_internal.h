@@ -338,6 +338,7 @@ struct Ctx {
     // n ceil, DP band half-width
     int32_t *len_tab = nullptr;      // [4][MAXLEN + 1]
     S2AState *s2a = nullptr;         // sam2aln rows and results (mh_sam2aln_csv)
+    int64_t s2a_serial = 0;          // calls that rebuilt *s2a so far (mh_sam2aln_serial)
     CensorState *censor = nullptr;   // censored FASTQ of the last mh_censor_fastq
     A2CState **a2c = nullptr;        // aln2counts row tables (mh_a2c_*), one per slot
     int64_t len_tab_key = -1;        // len_tab_key() of the parameters the tables hold

@@ -498,8 +498,15 @@ struct TextSink {
     int fd = -1;
     int64_t pos = 0;
     int err = 0;    // errno of a failed write
-    void put(std::string &s)
+    // the crc32 of everything put so far, kept when want_crc: joined from the
+    // pieces' own (piece_crc: computed by the thread that formatted the piece)
+    bool want_crc = false;
+    uint32_t crc = 0;
+    void put(std::string &s, const uint32_t *piece_crc = nullptr)
     {
+        if (want_crc)
+            crc = crc32_join(crc, piece_crc ? *piece_crc : crc32_update(0, s.data(), s.size()),
+                             (int64_t)s.size());
         if (out) {
             if (!s.empty()) out->push_back(std::move(s));
             return;
@@ -532,6 +539,7 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
         return;
     }
     std::vector<std::string> buf((size_t)nj);
+    std::vector<uint32_t> crc(sink.want_crc ? (size_t)nj : 0);
     std::unique_ptr<std::atomic<int>[]> done(new std::atomic<int>[(size_t)nj]);
     for (int64_t j = 0; j < nj; ++j) done[j].store(0);
     std::atomic<int64_t> next(0);
@@ -543,6 +551,8 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
             try {
                 for (int64_t j; !failed && (j = next.fetch_add(1)) < nj;) {
                     fn(buf[(size_t)j], j * STREAM_ROWS, std::min(n, (j + 1) * STREAM_ROWS));
+                    if (sink.want_crc)
+                        crc[(size_t)j] = crc32_update(0, buf[(size_t)j].data(), buf[(size_t)j].size());
                     done[j].store(1, std::memory_order_release);
                 }
             } catch (...) {
@@ -554,22 +564,21 @@ static void parallel_text(int64_t n, int nt, TextSink &sink,
         for (int64_t j = 0; j < nj && !failed && !sink.err; ++j) {
             while (!done[j].load(std::memory_order_acquire) && !failed) std::this_thread::yield();
             if (failed) break;
-            sink.put(buf[(size_t)j]);
+            sink.put(buf[(size_t)j], sink.want_crc ? &crc[(size_t)j] : nullptr);
         }
         failed = 1;   // a write error: the formatters stop at their next job
     });
 }
 
-// aligned.csv (sam2aln.py:459-478): per rname in first-seen order and per
-// q-cutoff, the distinct merged sequences sorted by (count, gap prefix, sequence), all
-// descending; seq written without its leading / trailing gaps
-static void s2a_aligned(const S2AState &S, TextSink &out)
+// aligned.csv's row order (sam2aln.py:459-478): per rname in first-seen order
+// and per q-cutoff, the distinct merged sequences sorted by (count, gap
+// prefix, sequence), all descending; groups without rows are left out
+void s2a_order(S2AState &S)
 {
+    S2AOrder &O = S.order;
+    if (O.valid) return;
+    O = S2AOrder();
     const int nt = s2a_threads();
-    {
-        std::string head("refname,qcut,rank,count,offset,seq\n");
-        out.put(head);
-    }
     const int nn = (int)S.names.size(), nc = (int)S.q_cutoffs.size();
     std::vector<int32_t> mref(S.n_merge);
     for (int64_t u = 0; u < (int64_t)S.u1.size(); ++u)
@@ -617,9 +626,9 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
                              (uint32_t)(S.res[4 * S.uniq[2 * k] + 1] ^ (int32_t)0x80000000);
     });
     auto by_key = [&](int64_t x, int64_t y) { return key[(size_t)x] > key[(size_t)y]; };
+    O.rows.resize((size_t)S.n_unique);
+    O.g_first.assign(1, 0);
     for (int g : order) {
-        const int r = g / nc;
-        const int32_t qcut = S.q_cutoffs[g % nc];
         auto &v = by[g];
         if (v.empty()) continue;
         parallel_sort(v, by_key, nt);
@@ -632,10 +641,47 @@ static void s2a_aligned(const S2AState &S, TextSink &out)
             for (size_t j; (j = next_run.fetch_add(1)) + 1 < runs.size();)
                 if (runs[j + 1] - runs[j] > 1) std::sort(v.begin() + runs[j], v.begin() + runs[j + 1], cmp);
         });
+        const int64_t at = O.g_first.back(), n = (int64_t)v.size();
+        const int np = n < 65536 ? 1 : nt;
+        std::vector<uint64_t> part((size_t)np, 0);
+        par_for(np, [&](int t) {
+            uint64_t sum = 0;
+            for (int64_t i = n * t / np; i < n * (t + 1) / np; ++i) {
+                O.rows[(size_t)(at + i)] = (int32_t)v[(size_t)i];
+                sum += (uint32_t)S.uniq[2 * v[(size_t)i] + 1];
+            }
+            part[(size_t)t] = sum;
+        });
+        uint64_t total = 0;
+        for (uint64_t x : part) total += x;
+        O.g_name.push_back(g / nc);
+        O.g_qcut.push_back(S.q_cutoffs[g % nc]);
+        O.g_total.push_back(total);
+        O.g_first.push_back(at + n);
+        std::vector<int64_t>().swap(v);
+    }
+    O.valid = true;
+}
+
+// aligned.csv: the rows of S.order; seq written without its leading /
+// trailing gaps
+static void s2a_aligned(S2AState &S, TextSink &out)
+{
+    const int nt = s2a_threads();
+    {
+        std::string head("refname,qcut,rank,count,offset,seq\n");
+        out.put(head);
+    }
+    s2a_order(S);
+    const S2AOrder &O = S.order;
+    for (size_t g = 0; g < O.g_name.size(); ++g) {
+        const int32_t qcut = O.g_qcut[g];
+        const int32_t *v = O.rows.data() + O.g_first[g];
+        const std::string &name = S.names[(size_t)O.g_name[g]];
         std::string ref;
-        csv_field(ref, S.names[r].data(), S.names[r].size());
+        csv_field(ref, name.data(), name.size());
         const size_t row_guess = ref.size() + 40 + (S.n_unique ? (size_t)(S.gathered.size() / S.n_unique) : 0);
-        parallel_text((int64_t)v.size(), nt, out, [&](std::string &o, int64_t a, int64_t b) {
+        parallel_text(O.g_first[g + 1] - O.g_first[g], nt, out, [&](std::string &o, int64_t a, int64_t b) {
             o.reserve(o.size() + (size_t)(b - a) * row_guess);
             for (int64_t rank = a; rank < b; ++rank) {
                 const int64_t k = v[rank], rep = S.uniq[2 * k];
@@ -714,7 +760,7 @@ static void s2a_failed(const S2AState &S, TextSink &out, int64_t u0, int64_t u1,
     });
 }
 
-static void s2a_emit(const S2AState &S, int which, TextSink &sink)
+static void s2a_emit(S2AState &S, int which, TextSink &sink)
 {
     const int64_t nu = (int64_t)S.u1.size();
     if (which == 0) s2a_aligned(S, sink);
@@ -733,7 +779,7 @@ int s2a_format_units(const S2AState &S, int which, int64_t u0, int64_t u1, bool 
     return 0;
 }
 
-int s2a_format(const S2AState &S, int which, std::vector<std::string> &out)
+int s2a_format(S2AState &S, int which, std::vector<std::string> &out)
 {
     out.clear();
     TextSink sink;
@@ -742,13 +788,15 @@ int s2a_format(const S2AState &S, int which, std::vector<std::string> &out)
     return 0;
 }
 
-int s2a_format_write(const S2AState &S, int which, int fd, int64_t offset, int64_t *written)
+int s2a_format_write(S2AState &S, int which, int fd, int64_t offset, int64_t *written, uint32_t *crc)
 {
     TextSink sink;
     sink.fd = fd;
     sink.pos = offset;
+    sink.want_crc = crc != nullptr;
     s2a_emit(S, which, sink);
     if (written) *written = sink.pos - offset;
+    if (crc) *crc = sink.crc;
     return sink.err;
 }
 

@@ -530,10 +530,7 @@ extern "C" int mh_sam2aln_part(mh_ctx *ctx, int fd, int part, int parts, int q_c
     S2AState &S = *state_of(ctx);
     const int rc = guarded("mh_sam2aln_part", [&]() -> int {
         S.q_cutoffs.assign(1, q_cutoff);   // the sharded pass takes one q-cutoff
-        S.n_merge = S.n_unique = 0;
-        S.res.clear();
-        for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
-        S.out_valid = 0;
+        s2a_begin(c, S);                   // (a part's state never becomes `complete`)
         // the header row and the qname column
         const char *p = text, *end = text + len;
         std::vector<std::string> head;

@@ -26,6 +26,16 @@ constexpr int S2A_MAX_CUTS = 8;  // q-cutoffs of one call (SAM2ALN_Q_CUTOFFS, sa
 struct S2AShard;                 // sam2aln split over the ranks of a job (mh_s2a_shard.cpp)
 void s2a_shard_free(S2AShard *sh);
 
+// aligned.csv's data rows in file order (s2a_order): the printed groups, one
+// per (rname, q-cutoff) that has rows, and per row its index into uniq
+struct S2AOrder {
+    bool valid = false;
+    std::vector<int32_t> g_name, g_qcut;   // per group: index into names, the cutoff
+    std::vector<int64_t> g_first;          // per group (+ end): its first row
+    std::vector<uint64_t> g_total;         // per group: the sum of its rows' counts
+    std::vector<int32_t> rows;             // per row: k of uniq[2k], uniq[2k + 1]
+};
+
 struct S2AState {
     // ---- rows of the last remap.csv (host) ----
     int64_t n_rows = 0;
@@ -78,6 +88,13 @@ struct S2AState {
     // ---- formatted outputs (cached between the size query and the copy) ----
     std::vector<std::string> out_cache[3];   // the text as pieces, in order
     int out_valid = 0;
+    S2AOrder order;                     // aligned.csv's row order, built on first use
+    // true from the end of a whole (un-sharded) call that succeeded until
+    // the next call starts: the device arrays then hold what the host ones do
+    bool complete = false;
+    // crc32 and size of aligned.csv as mh_sam2aln_write last wrote it (-1: not written)
+    uint32_t wr_crc = 0;
+    int64_t wr_bytes = -1;
     // ---- host timings of the last call (ms) ----
     double t_parse = 0, t_device = 0, t_format[3] = {0, 0, 0};
     // ---- this rank's part of a sharded sam2aln ----
@@ -95,15 +112,34 @@ inline bool s2a_many_ns(const S2AState &S, int64_t m)
     return false;
 }
 
+// Every call that rebuilds S starts here: a new serial (mh_sam2aln_serial),
+// nothing of the last call's results stands any more.
+inline void s2a_begin(Ctx &c, S2AState &S)
+{
+    ++c.s2a_serial;
+    S.complete = false;
+    S.order = S2AOrder();
+    S.wr_bytes = -1;
+    S.n_merge = S.n_unique = 0;
+    S.res.clear();
+    for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
+    S.out_valid = 0;
+}
+
 // host half: the header row of text, then its records (body_lo >= 0: only
 // the records in bytes [body_lo, body_hi) of text, both record boundaries)
 int s2a_parse(S2AState &S, const char *text, int64_t len, int64_t body_lo = -1, int64_t body_hi = -1);
 // insert.csv (which 1) or failed.csv (2) rows of units [u0, u1)
 int s2a_format_units(const S2AState &S, int which, int64_t u0, int64_t u1, bool head_row,
                      std::vector<std::string> &out);
-int s2a_format(const S2AState &S, int which, std::vector<std::string> &out);
-// the same text written to fd from offset while it is formatted; 0 or errno
-int s2a_format_write(const S2AState &S, int which, int fd, int64_t offset, int64_t *written);
+// aligned.csv's row order into S.order (kept until the next call rebuilds S):
+// the formatter and mh_a2c_load_resident both read the rows from it
+void s2a_order(S2AState &S);
+int s2a_format(S2AState &S, int which, std::vector<std::string> &out);
+// the same text written to fd from offset while it is formatted; 0 or errno.
+// crc (may be null): the crc32 of the bytes written, from the pieces' own
+int s2a_format_write(S2AState &S, int which, int fd, int64_t offset, int64_t *written,
+                     uint32_t *crc = nullptr);
 // device half.  dev: the row arrays are on the device already (k_s2a_stage
 // wrote them) and span[r] is row r's reference span; without it they are
 // uploaded from S and the spans come from S.cig

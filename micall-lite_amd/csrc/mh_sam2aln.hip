@@ -826,10 +826,7 @@ extern "C" int mh_sam2aln_csv_q(mh_ctx *ctx, const char *text, int64_t len, int 
     if (!c.s2a) c.s2a = new S2AState();
     S2AState &S = *c.s2a;
     S.q_cutoffs.assign(q_cutoffs, q_cutoffs + n_cut);
-    S.n_merge = S.n_unique = 0;
-    S.res.clear();
-    for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
-    S.out_valid = 0;
+    s2a_begin(c, S);
     S.staged_reads = -1;
     auto t0 = std::chrono::steady_clock::now();
     int pst = 0;
@@ -851,6 +848,7 @@ extern "C" int mh_sam2aln_csv_q(mh_ctx *ctx, const char *text, int64_t len, int 
     auto t2 = std::chrono::steady_clock::now();
     S.t_parse = std::chrono::duration<double, std::milli>(t1 - t0).count();
     S.t_device = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    S.complete = true;
     if (n_units) *n_units = (int64_t)S.u1.size();
     return 0;
 }
@@ -931,10 +929,7 @@ extern "C" int mh_sam2aln_resident(mh_ctx *ctx, int n_refs, const char *const *r
     if (!c.s2a) c.s2a = new S2AState();
     S2AState &S = *c.s2a;
     S.q_cutoffs.assign(q_cutoffs, q_cutoffs + n_cut);
-    S.n_merge = S.n_unique = 0;
-    S.res.clear();
-    for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
-    S.out_valid = 0;
+    s2a_begin(c, S);
     S.u1.clear();
     std::vector<int32_t> sam_ref, span_ins;
     int st = 0;
@@ -961,6 +956,7 @@ extern "C" int mh_sam2aln_resident(mh_ctx *ctx, int n_refs, const char *const *r
     const auto t3 = std::chrono::steady_clock::now();
     S.t_parse = std::chrono::duration<double, std::milli>(t2 - t1).count();
     S.t_device = std::chrono::duration<double, std::milli>((t1 - t0) + (t3 - t2)).count();
+    S.complete = true;
     if (n_units) *n_units = (int64_t)S.u1.size();
     return 0;
 }
@@ -1037,8 +1033,11 @@ extern "C" int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, 
         S2AState &S = *c.s2a;
         auto t0 = std::chrono::steady_clock::now();
         int err = 0;
+        int64_t n = 0;
+        uint32_t crc = 0;
+        if (which == 0) S.wr_bytes = -1;
         try {
-            err = s2a_format_write(S, which, fd, offset, written);
+            err = s2a_format_write(S, which, fd, offset, &n, which == 0 ? &crc : nullptr);
         } catch (const std::exception &e) {
             set_error("mh_sam2aln_write: out of memory (%s)", e.what());
             return -2;
@@ -1046,22 +1045,48 @@ extern "C" int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, 
         S.t_format[which] = std::chrono::duration<double, std::milli>(
                                 std::chrono::steady_clock::now() - t0).count();
         if (err) { set_error("mh_sam2aln_write: write failed (%s)", strerror(err)); return -4; }
+        if (written) *written = n;
+        if (which == 0) { S.wr_crc = crc; S.wr_bytes = n; }
         return 0;
     }
     size_t used = 0;
     if (int st = mh_sam2aln_output(ctx, which, nullptr, 0, &used)) return st;
     S2AState &S = *ctx_of(ctx)->s2a;
     int64_t pos = offset;
+    uint32_t crc = 0;
+    if (which == 0) S.wr_bytes = -1;
     for (const std::string &piece : S.out_cache[which]) {
         if (const int e = write_all_at(fd, piece.data(), piece.size(), pos)) {
             set_error("mh_sam2aln_write: write failed (%s)", strerror(e));
             return -4;
         }
+        if (which == 0) crc = crc32_join(crc, crc32_update(0, piece.data(), piece.size()), (int64_t)piece.size());
         pos += (int64_t)piece.size();
     }
     if (written) *written = pos - offset;
+    if (which == 0) { S.wr_crc = crc; S.wr_bytes = pos - offset; }
     std::vector<std::string>().swap(S.out_cache[which]);
     S.out_valid &= ~(1 << which);
+    return 0;
+}
+
+extern "C" int mh_sam2aln_written(mh_ctx *ctx, int which, uint32_t *crc, int64_t *bytes)
+{
+    if (!ctx || which != 0 || !crc || !bytes) return -3;
+    Ctx &c = *ctx_of(ctx);
+    if (!c.s2a || c.s2a->wr_bytes < 0) {
+        set_error("mh_sam2aln_written: aligned.csv was not written by mh_sam2aln_write");
+        return -3;
+    }
+    *crc = c.s2a->wr_crc;
+    *bytes = c.s2a->wr_bytes;
+    return 0;
+}
+
+extern "C" int mh_sam2aln_serial(mh_ctx *ctx, int64_t *serial)
+{
+    if (!ctx || !serial) return -3;
+    *serial = ctx_of(ctx)->s2a_serial;
     return 0;
 }
 

@@ -134,6 +134,9 @@ def _declare(L):
         'mh_sam2aln_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _I64P], ctypes.c_int),
         'mh_sam2aln_write': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_stats': ([_P, _P], ctypes.c_int),
+        'mh_sam2aln_written': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _I64P], ctypes.c_int),
+        'mh_sam2aln_serial': ([_P, _I64P], ctypes.c_int),
+        'mh_a2c_load_resident': ([_P, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
         'mh_a2c_part_open': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
                               _I64P], ctypes.c_int),
         'mh_a2c_part_groups': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
@@ -510,6 +513,24 @@ class Context:
         check(lib().mh_sam2aln_write(self.h, w, int(fd), int(offset), ctypes.byref(n)), 'mh_sam2aln_write')
         return n.value
 
+    def sam2aln_written(self, which='aligned'):
+        """(crc32, bytes) of aligned.csv as the last sam2aln_write wrote it
+        (mh_sam2aln_written; the checksum of the formatted pieces, nothing is
+        read back), None when it was not written that way."""
+        w = {'aligned': 0, 'insert': 1, 'failed': 2}[which]
+        crc, n = ctypes.c_uint32(), ctypes.c_int64()
+        if lib().mh_sam2aln_written(self.h, w, ctypes.byref(crc), ctypes.byref(n)) != 0:
+            return None
+        return crc.value, n.value
+
+    @property
+    def sam2aln_serial(self):
+        """mh_sam2aln_serial: how many calls have rebuilt this context's
+        sam2aln results (session.aligned_resident compares it)."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_serial(self.h, ctypes.byref(n)), 'mh_sam2aln_serial')
+        return n.value
+
     def sam2aln_output(self, which):
         """'aligned' | 'insert' | 'failed' CSV text of the last sam2aln."""
         w = {'aligned': 0, 'insert': 1, 'failed': 2}[which]
@@ -599,6 +620,18 @@ class Context:
         if st == 1:
             return None
         check(st, 'mh_a2c_load_file')
+        return n.value
+
+    def a2c_load_resident(self, slot, codon_chars):
+        """mh_a2c_load_resident: the table a2c_load_file would build from the
+        aligned.csv of this context's last sam2aln call, from that call's
+        results on the device: number of groups, or None when the rows
+        cannot stand for the file (load the file instead)."""
+        n = ctypes.c_int64()
+        st = lib().mh_a2c_load_resident(self.h, slot, codon_chars, ctypes.byref(n))
+        if st == 1:
+            return None
+        check(st, 'mh_a2c_load_resident')
         return n.value
 
     def a2c_inserts_text(self, slot, g, frame, lefts, rights, lead, targets, eol):

@@ -32,6 +32,13 @@ unchanged.  Differences that never reach an output file:
     device, so its nuc_seqs stays empty;
   * characters other than A C G T N - n, negative offsets and counts of 2**32
     or more raise NativeError.
+When aligned_csv is the unchanged file this process's sam2aln() just wrote
+from results that are still on the device (session.aligned_resident), the
+file is not parsed: the rows, the codon extents and the bin lists are built
+on the device from those results (mh_a2c_load_resident) and the reports are
+the same bytes.  session.stats['aln2counts_source'] says which way a call
+went ('device' or 'csv'); MICALL_ALN2COUNTS_RESIDENT=0 in the environment
+forces the file path.
 There is no CPU path: without libmicall_hip.so or a device the first call
 raises NativeUnavailable.
 """
@@ -752,6 +759,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     global _SHARD
     sh = session.shard()
     SHARD_STATS.clear()
+    session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
                coverage_summary_csv)
     with session.writer_stage(*handles) as stage:
@@ -853,8 +861,17 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if source:
         report.enable_callback(callback, os.stat(source).st_size)
     ctx = session.context()
+    session.stats['aln2counts_source'] = 'csv'
     if groups is None:           # not loaded by the ranks of a sharded job
-        fd = session.readable_fd(aligned_csv)
+        if (os.environ.get('MICALL_ALN2COUNTS_RESIDENT', '1') != '0' and
+                session.aligned_resident(ctx, aligned_csv)):
+            # the file this process's sam2aln() just wrote: its rows are on
+            # the device already (None: they cannot stand for the file)
+            groups = ctx.a2c_load_resident(SLOT_REPORT, _CODON_CHARS)
+            if groups is not None:
+                aligned_csv.seek(0, 2)
+                session.stats['aln2counts_source'] = 'device'
+        fd = session.readable_fd(aligned_csv) if groups is None else None
         if fd is not None:   # the file mmap'd by the library (no '\r' in it)
             groups = ctx.a2c_load_file(SLOT_REPORT, fd, _CODON_CHARS)
             if groups is not None:

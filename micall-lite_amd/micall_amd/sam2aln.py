@@ -19,6 +19,10 @@ the rows are built on the device from the resident reads and records
 session.stats['sam2aln_source'] says which way a call went ('device' or
 'csv'); MICALL_SAM2ALN_RESIDENT=0 in the environment forces the file path.
 
+The aligned.csv a call wrote is recorded (session.aligned_written) when it
+is exactly the text the library formatted, so that aln2counts() in the same
+process can count the rows where they are instead of parsing the file.
+
 In a sharded job (torchrun) every rank takes its share of remap.csv's rows,
 merges its pairs on its GPU, and writes its own insert.csv / failed.csv rows
 and its piece of aligned.csv at all-gathered offsets; the distinct merged
@@ -68,6 +72,7 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     sh = session.shard()
     SHARD_STATS.clear()
     session.stats['sam2aln_source'] = 'csv'
+    session.aligned_forget()     # recorded again below, once aligned.csv is these results
     use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
     if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts):
         return
@@ -91,7 +96,9 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
             ctx.sam2aln_csv(text, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
-                _write_output(ctx, which, handle)
+                start = _write_output(ctx, which, handle)
+                if which == 'aligned':
+                    _record_aligned(ctx, handle, start, sh)
 
 
 SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitters
@@ -181,15 +188,34 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
 
 def _write_output(ctx, which, handle):
     """One output: written by the library at the handle's position when it is
-    a plain file (pwrite), else through the handle."""
+    a plain file (pwrite), else through the handle.  Returns the file offset
+    the library wrote from, None when the text went through the handle."""
     from .sharded_io import SharedOutput
     out = SharedOutput(None, handle)
     if out.direct:
         # formatted and written together (pwrite from the handle's position)
-        out.end += ctx.sam2aln_write(which, out.fd, int(out.end))
+        start = int(out.end)
+        out.end += ctx.sam2aln_write(which, out.fd, start)
         out.finish()
+        return start
+    handle.write(ctx.sam2aln_output(which))
+    return None
+
+
+def _record_aligned(ctx, handle, start, sh):
+    """aln2counts() may count the rows on the device instead of parsing
+    aligned.csv when the file is exactly what the library just wrote: one
+    process, written from offset 0 of a plain file that now ends where the
+    write did (session.aligned_resident tests the rest when it is read)."""
+    written = ctx.sam2aln_written('aligned') if sh is None and start == 0 else None
+    try:
+        whole = written is not None and os.fstat(handle.fileno()).st_size == written[1]
+    except (AttributeError, OSError, ValueError):
+        whole = False
+    if whole:
+        session.aligned_written(ctx, handle, written)
     else:
-        handle.write(ctx.sam2aln_output(which))
+        session.aligned_forget()
 
 
 def parseArgs():

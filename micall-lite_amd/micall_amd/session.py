@@ -33,8 +33,9 @@ _shard = None
 _shard_checked = False
 _prelim = None     # what the last prelim_map() of this process wrote (prelim_written)
 _remap = None      # what the last remap() of this process wrote (remap_written)
+_aligned = None    # what the last sam2aln() of this process wrote (aligned_written)
 # how the last calls ran: remap sets 'prelim_source', sam2aln 'sam2aln_source',
-# each to 'device' or 'csv'
+# aln2counts 'aln2counts_source', each to 'device' or 'csv'
 stats = {}
 
 
@@ -265,8 +266,9 @@ def _written(ctx, handle, checksum, **more):
             pass
         ident = _file_identity(handle)
         settled = ident is not None and _wait_past(ident[4])
-    return dict(identity=ident, settled=settled, checksum=checksum, serial=ctx.map_serial, key=_key,
-                **more)
+    if 'serial' not in more:
+        more['serial'] = ctx.map_serial
+    return dict(identity=ident, settled=settled, checksum=checksum, key=_key, **more)
 
 
 def _unchanged_file(p, handle):
@@ -352,20 +354,49 @@ def remap_refnames():
     return list(_remap['refnames'])
 
 
+def aligned_written(ctx, handle, checksum=None):
+    """Record that sam2aln() wrote `handle` (aligned.csv) from the results
+    that are on the device now (ctx.sam2aln_serial).  Kept like
+    remap_written keeps remap.csv: the file's identity after the last write
+    and, when known, (crc32, size) of its content as formatted.  The results
+    belong to the sam2aln state, whatever reads are resident."""
+    global _aligned
+    _aligned = _written(ctx, handle, checksum, serial=ctx.sam2aln_serial)
+
+
+def aligned_forget():
+    """aligned.csv is not (only) the resident results: aln2counts() parses it."""
+    global _aligned
+    _aligned = None
+
+
+def aligned_resident(ctx, handle):
+    """True when `handle` is the aligned.csv this process's last sam2aln()
+    wrote from the results still on the device, unchanged (as
+    prelim_resident tests prelim.csv), not read from yet and readable by the
+    native parser: aln2counts() then counts the device rows
+    (Context.a2c_load_resident) instead of parsing the file."""
+    p = _aligned
+    return (p is not None and p['serial'] == ctx.sam2aln_serial and shard() is None and
+            _unchanged_file(p, handle) and readable_fd(handle) is not None)
+
+
 def invalidate():
     """The resident reads were replaced (e.g. by split re-mapping)."""
-    global _key, _prelim, _remap
+    global _key, _prelim, _remap, _aligned
     _key = None
     _prelim = None
     _remap = None
+    _aligned = None
 
 
 def reset():
     """Close the process-wide context (the next call creates a new one)."""
-    global _ctx, _key, _prelim, _remap
+    global _ctx, _key, _prelim, _remap, _aligned
     if _ctx is not None:
         _ctx.close()
     _ctx = None
     _key = None
     _prelim = None
     _remap = None
+    _aligned = None
