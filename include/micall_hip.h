@@ -220,6 +220,21 @@ int mh_map_stats(mh_ctx *ctx, int64_t *out5);
  * sizes them again. */
 int mh_test_set_capacities(mh_ctx *ctx, int64_t cigar_pool_words, int64_t pileup_events,
                            int64_t pileup_event_bytes, int64_t token_bytes);
+/* Test entry point, read-only: the launch shapes of the last mh_pileup and of
+ * the token aggregation behind it (mh_pileup_dims / mh_pileup_events), so a
+ * test can assert that its input took the path it was built for.
+ *   out16[0..6]  constants: reference span per mate expanded with all loads
+ *                in flight (PU_XCH * 64), MH_MAXOPS, PU_INSBUF (merged
+ *                insertion bytes per unit), PU_MAXINS, TOK_LDS_SLOTS,
+ *                TOK_LDS_KEYS, MH_PILEUP_SLACK
+ *   out16[7..10] k_pileup: blocks, waves per block, LDS window words, units
+ *   out16[11..14] k_tok_insert blocks, k_tok_count blocks, events, distinct keys
+ *                (0 until the tokens were aggregated)
+ *   out16[15]    references of that pileup
+ *   win_len[r]   r < n_refs: positions of reference r's LDS window, 0 without
+ *                one, -1 for a reference mh_pileup_only left out
+ * ctx may be NULL: the constants alone. */
+int mh_test_pileup_info(mh_ctx *ctx, int64_t *out16, int n_refs, int32_t *win_len);
 /* Test entry point: on != 0 gives every reference set of later
  * mh_index_build calls the same cache signature, so only the comparison of
  * the cached bytes tells two sets apart. */

@@ -238,6 +238,14 @@ struct PileState {
     int64_t tok_meta_cap = 0, tok_bytes_cap = 0;
     char *tok_pin = nullptr;        // pinned staging of the gather's first round trip
     size_t tok_pin_cap = 0;
+    // launch shapes of the last pileup and token aggregation, kept for
+    // mh_test_pileup_info (host bookkeeping; nothing reads them otherwise)
+    struct Info {
+        int64_t blocks = 0, n_units = 0;
+        int wpb = 0, win_words = 0;
+        std::vector<int32_t> win_map;
+        int64_t tok_insert_blocks = 0, tok_count_blocks = 0, tok_ne = 0, tok_nd = 0;
+    } info;
 };
 
 // ---- kernels' host-side launchers (defined in the .hip files) ----------

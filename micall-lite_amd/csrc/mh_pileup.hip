@@ -4,7 +4,7 @@
 //   merge_reads    remap.py:86-126    which mates count, the rname check
 //   apply_cigar    sam2aln.py:84-153  each mate in reference coordinates
 //   merge_pairs    sam2aln.py:156-237 per-position merge, lane-parallel
-//   merge_inserts  sam2aln.py:240-273 (lane 0; rare)
+//   merge_inserts  sam2aln.py:240-273 (lane-parallel per insertion; rare)
 //   update_counts  remap.py:271-306   int32 atomics into dense A/C/G/T
 //                                     counters, 'N'/'-' flags, sparse events
 // The refmap of the reference is order-independent except for its key
@@ -16,10 +16,19 @@
 
 namespace mh {
 
-constexpr int PU_INSBUF = 2048;   // merged insertion bytes per unit
+// Merged insertion bytes per unit.  A pair of reads of <= 1024 bases needs
+// at most 3 * 1024: mate 1's insertions (<= its length), then one merged
+// string per insertion of mate 2, each as long as the longer of the two at
+// its key (<= both mates' lengths together).  A unit that needs more is
+// refused by name (PILE_ERR_INSBUF), never counted short.
+constexpr int PU_INSBUF = 3 * 1024;
 constexpr int PU_MAXINS = 2 * MH_MAXOPS;
 constexpr int PU_LDS = 160 * 1024 - 64;   // dynamic LDS (the static s_next beside it)
 constexpr int PU_XCH = 5;        // 64-position chunks per mate expanded with all loads in flight
+// ev_ctr[3]: 0, or the error of the last unit that reported one (a plain
+// exchange: any of them fails the pileup): a malformed row (CIGAR /
+// position); a unit whose merged insertions do not fit in PU_INSBUF
+constexpr unsigned long long PILE_ERR_ROW = 1, PILE_ERR_INSBUF = 2;
 
 struct RowV {
     int present, flag, ref, pos, n_cigar, rev, m;
@@ -219,10 +228,13 @@ __device__ inline UnitView unit_view(unsigned char *base, int span)
 
 // Merged insertions of the unit a wave is on (rare: units with I ops), in a
 // per-wave slice of global scratch: key, offset and length of each entry and
-// the merged bytes.
-constexpr int PU_INS_BYTES = 3 * 4 * PU_MAXINS + PU_INSBUF;
+// the merged bytes (offsets and lengths <= PU_INSBUF fit 16 bits, which
+// keeps a wave's slice at 5 KiB).
+static_assert(PU_INSBUF < 32768, "InsView offsets are int16");
+constexpr int PU_INS_BYTES = (4 + 2 + 2) * PU_MAXINS + PU_INSBUF;
 struct InsView {
-    int32_t *key, *off, *len;
+    int32_t *key;
+    int16_t *off, *len;
     char *buf;
 };
 
@@ -230,9 +242,9 @@ __device__ inline InsView ins_view(char *base)
 {
     InsView v;
     v.key = (int32_t *)base;
-    v.off = v.key + PU_MAXINS;
-    v.len = v.key + 2 * PU_MAXINS;
-    v.buf = (char *)(v.key + 3 * PU_MAXINS);
+    v.off = (int16_t *)(v.key + PU_MAXINS);
+    v.len = v.off + PU_MAXINS;
+    v.buf = (char *)(v.len + PU_MAXINS);
     return v;
 }
 
@@ -351,7 +363,7 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
         if (nm == 0) continue;                                 // remap.py:111-112
         const int ref = r1.ref;
         if (ref < 0 || ref >= A.n_refs) {
-            if (lane == 0) atomicExch(&A.ev_ctr[3], 1ull);
+            if (lane == 0) atomicExch(&A.ev_ctr[3], PILE_ERR_ROW);
             continue;
         }
         // a reference this pileup does not count (mh_pileup_only)
@@ -415,7 +427,7 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
             else { padA = mk.pos - 1; lenA = padA + rf0; oneA = onek; }
         }
         if (bad) {
-            if (lane == 0) atomicExch(&A.ev_ctr[3], 1ull);
+            if (lane == 0) atomicExch(&A.ev_ctr[3], PILE_ERR_ROW);
             continue;
         }
         __builtin_amdgcn_wave_barrier();
@@ -566,10 +578,6 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
                     }
                     mn = wave_min_all(mn);
                     if (!(mn > cut)) continue;
-                    if (used + 2 * il + 2 > PU_INSBUF) {
-                        if (lane == 0) atomicExch(&A.ev_ctr[3], 1ull);
-                        continue;
-                    }
                     // an existing entry with the same key (ins1 vs ins2): the last one
                     int at = -1;
                     const uint64_t same = __builtin_amdgcn_ballot_w64(lane < n && keyv == key);
@@ -579,6 +587,10 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
                     char *dst = I.buf + used;
                     int outlen;
                     if (pass == 0) {
+                        if (used + il > PU_INSBUF) {
+                            if (lane == 0) atomicExch(&A.ev_ctr[3], PILE_ERR_INSBUF);
+                            continue;
+                        }
                         for (int x0 = 0; x0 < il; x0 += 64) {
                             char tc, tq;
                             if (x0 + lane < il) {
@@ -598,10 +610,9 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
                             const int r1 = __builtin_amdgcn_readfirstlane(L.opread(0)[o1]);
                             if (r1 + padA != key) continue;
                             l1 = (int)(op1 >> 4);
-                            if (l1 > PU_INSBUF / 8) l1 = PU_INSBUF / 8;
                             o1s = r1;
                         }
-                        const int l2 = il > PU_INSBUF / 8 ? PU_INSBUF / 8 : il;
+                        const int l2 = il;
                         // merge_pairs on the two strings (sam2aln.py:156-237): the
                         // shorter one plays seq1
                         const bool sw = l1 > l2;
@@ -610,6 +621,11 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
                         const int reva = sw ? v.rev : w.rev, ma = sw ? v.m : w.m;
                         const int revb = sw ? w.rev : v.rev, mb = sw ? w.m : v.m;
                         const int64_t roffa = sw ? v.roff : w.roff, roffb = sw ? w.roff : v.roff;
+                        // the merged string is as long as the longer of the two
+                        if (used + lb > PU_INSBUF) {
+                            if (lane == 0) atomicExch(&A.ev_ctr[3], PILE_ERR_INSBUF);
+                            continue;
+                        }
                         for (int i0 = 0; i0 < lb; i0 += 64) {
                             const int i = i0 + lane;
                             if (i >= lb) continue;
@@ -642,8 +658,8 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
                     if (at < 0) at = n++;
                     if (lane == 0) {
                         I.key[at] = key;
-                        I.off[at] = used;
-                        I.len[at] = outlen;
+                        I.off[at] = (int16_t)used;
+                        I.len[at] = (int16_t)outlen;
                     }
                     if (lane == at) keyv = key;
                     used += outlen;
@@ -810,7 +826,7 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
             atomicAdd(&rl[ref].read_count, 1u);
             atomicMin(&rl[ref].first_unit, (long long)u);
             if (mxp > 0) atomicMax(&rl[ref].max_pos, mxp);
-            if (err) atomicExch(&A.ev_ctr[3], 1ull);
+            if (err) atomicExch(&A.ev_ctr[3], PILE_ERR_ROW);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -1002,6 +1018,12 @@ int run_pileup(Ctx &c, int source, int q_cutoff)
     hipStream_t s = c.stream;
     PileGeometry geo;
     if (int st = pile_geometry(c, source, n_units, geo)) return st;
+    P.info.blocks = geo.blocks;
+    P.info.wpb = geo.wpb;
+    P.info.win_words = geo.win_words;
+    P.info.n_units = n_units;
+    P.info.win_map = geo.win_map;
+    P.info.tok_insert_blocks = P.info.tok_count_blocks = P.info.tok_ne = P.info.tok_nd = 0;
     {
         const int64_t need = geo.blocks * geo.wpb * (int64_t)PU_INS_BYTES;
         if (P.ins_scratch_bytes < need) {
@@ -1067,7 +1089,15 @@ int run_pileup(Ctx &c, int source, int q_cutoff)
         int64_t ctr[4];
         MH_HIP(hipMemcpyAsync(ctr, P.ev_counters, sizeof(ctr), hipMemcpyDeviceToHost, s));
         MH_HIP(hipStreamSynchronize(s));
-        if (ctr[3]) { set_error("mh_pileup: malformed alignment row (CIGAR/position)"); return -3; }
+        if (ctr[3] == (int64_t)PILE_ERR_INSBUF) {
+            set_error("mh_pileup: the merged insertions of one read pair exceed PU_INSBUF (%d bytes)",
+                      PU_INSBUF);
+            return -3;
+        }
+        if (ctr[3]) {
+            set_error("mh_pileup: malformed alignment row (CIGAR/position)");
+            return -3;
+        }
         if (!ctr[2]) return 0;
         // events or token bytes past their buffers: grow both to what the
         // launch asked for (the counters count every claim) and run it again
@@ -1318,6 +1348,10 @@ int run_token_aggregate(Ctx &c, int64_t ne, int64_t pool_used, std::vector<int32
         int32_t nd = 0, of = 0;
         std::memcpy(&nd, P.tok_pin, 4);
         std::memcpy(&of, P.tok_pin + 4, 4);
+        P.info.tok_insert_blocks = blocks;
+        P.info.tok_count_blocks = cblocks;
+        P.info.tok_ne = ne;
+        P.info.tok_nd = nd;
         if (nd <= 0) return 0;
         meta.resize(5 * (size_t)nd);
         std::memcpy(meta.data(), P.tok_pin + 16, 20 * (size_t)std::min<int64_t>(nd, K));
@@ -1415,6 +1449,31 @@ extern "C" int mh_pileup_exchange_bytes(mh_ctx *ctx, int n_sel, int64_t *sum_byt
     if (sum_bytes) *sum_bytes = sizeof(int32_t) * (4 * cells + c.pile.n_refs);
     if (max_bytes) *max_bytes = sizeof(int32_t) * 2 * c.pile.n_refs;
     if (flag_bytes) *flag_bytes = 2 * cells;
+    return 0;
+}
+
+extern "C" int mh_test_pileup_info(mh_ctx *ctx, int64_t *out16, int n_refs, int32_t *win_len)
+{
+    if (!out16 || n_refs < 0 || (n_refs > 0 && !win_len)) return -3;
+    const int64_t consts[7] = {PU_XCH * 64, MH_MAXOPS, PU_INSBUF, PU_MAXINS, TOK_LDS_SLOTS,
+                               TOK_LDS_KEYS, MH_PILEUP_SLACK};
+    for (int k = 0; k < 16; ++k) out16[k] = k < 7 ? consts[k] : 0;
+    for (int r = 0; r < n_refs; ++r) win_len[r] = 0;
+    if (!ctx) return 0;
+    const PileState::Info &I = reinterpret_cast<Ctx *>(ctx)->pile.info;
+    out16[7] = I.blocks;
+    out16[8] = I.wpb;
+    out16[9] = I.win_words;
+    out16[10] = I.n_units;
+    out16[11] = I.tok_insert_blocks;
+    out16[12] = I.tok_count_blocks;
+    out16[13] = I.tok_ne;
+    out16[14] = I.tok_nd;
+    out16[15] = (int64_t)I.win_map.size() / 2;
+    for (int r = 0; r < n_refs && 2 * (size_t)r + 1 < I.win_map.size(); ++r) {
+        const int32_t wo = I.win_map[2 * (size_t)r];
+        win_len[r] = wo >= 0 ? I.win_map[2 * (size_t)r + 1] : (wo == -2 ? -1 : 0);
+    }
     return 0;
 }
 

@@ -82,6 +82,7 @@ def _declare(L):
         'mh_recs_fetch': ([_P, ctypes.c_int64, ctypes.c_int64, _P], ctypes.c_int),
         'mh_test_set_capacities': ([_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64], ctypes.c_int),
+        'mh_test_pileup_info': ([_P, _P, ctypes.c_int, _P], ctypes.c_int),
         'mh_test_force_index_collision': ([_P, ctypes.c_int], ctypes.c_int),
         'mh_retry_counts': ([_P, _P], ctypes.c_int),
         'mh_test_set_gotoh_wait': ([_P, ctypes.c_int64], ctypes.c_int),
@@ -308,6 +309,23 @@ def device_count():
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+PILEUP_INFO_FIELDS = ('xch_span', 'max_ops', 'ins_buf', 'max_ins', 'tok_lds_slots', 'tok_lds_keys',
+                      'pileup_slack', 'blocks', 'wpb', 'win_words', 'n_units', 'tok_insert_blocks',
+                      'tok_count_blocks', 'tok_events', 'tok_keys', 'n_refs')
+
+
+def pileup_info(handle=None, n_refs=0):
+    """mh_test_pileup_info: dict of PILEUP_INFO_FIELDS plus 'win_len' (per
+    reference: LDS window positions, 0 none, -1 left out).  Without a
+    context handle only the library's constants are set (needs no GPU)."""
+    out = np.zeros(16, dtype=np.int64)
+    win = np.zeros(max(n_refs, 1), dtype=np.int32)
+    check(lib().mh_test_pileup_info(handle, _ptr(out), n_refs, _ptr(win)), 'mh_test_pileup_info')
+    info = dict(zip(PILEUP_INFO_FIELDS, (int(x) for x in out)))
+    info['win_len'] = win[:n_refs].tolist()
+    return info
 
 
 def params(mode, rdg=(10, 3), rfg=(10, 3), maxins=1200):
@@ -1010,6 +1028,13 @@ class Context:
                                            pileup_event_bytes, token_bytes),
               'mh_test_set_capacities')
         self.map_serial += 1
+
+    def test_pileup_info(self):
+        """Test entry point: launch shapes of the last pileup and token
+        aggregation and the library's pileup constants (pileup_info)."""
+        n = ctypes.c_int()
+        check(lib().mh_pileup_dims(self.h, ctypes.byref(n), None, None, None), 'mh_pileup_dims')
+        return pileup_info(self.h, n.value)
 
     def test_force_index_collision(self, on=True):
         """Test entry point: every later index_build gets the same cache

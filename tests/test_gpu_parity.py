@@ -3,13 +3,13 @@ same seeded inputs (bit-exact: every SAM field and CIGAR op, every pileup
 counter), and against the reference-generated golden vectors."""
 import json
 import os
-import re
 from collections import Counter
 
 import numpy as np
 import pytest
 
 import oracle
+import pileup_path_cases
 from micall_amd import _native, projects, synth
 
 pytestmark = pytest.mark.gpu
@@ -356,38 +356,11 @@ def test_pileup_rows_leading_gaps_vs_oracle(ctx, q):
 
 def _rows_case_vs_oracle(ctx, sam, quality_cutoff):
     """One SAM text through source 1 (rows) against the oracle pileup."""
-    ref_names, pairs = oracle.matchmaker(sam.splitlines(True))
+    ref_names, pairs, args = pileup_path_cases.rows_of(sam)
     want_refmap, want_counts = oracle.pileup(ref_names, pairs, quality_cutoff)
-    rows, units = [], []
-    for r1, r2 in pairs:
-        ids = []
-        for r in (r1, r2):
-            if r is None:
-                ids.append(-1)
-            else:
-                ids.append(len(rows))
-                rows.append(r)
-        units += ids
-    flag = [int(r[1]) for r in rows]
-    ref = [ref_names.index(r[2]) for r in rows]
-    pos = [int(r[3]) for r in rows]
-    cig, cig_off, n_cig = [], [], []
-    for r, f in zip(rows, flag):
-        ops = oracle.parse_cigar(r[5]) if not (f & 4) else []
-        cig_off.append(len(cig))
-        n_cig.append(len(ops))
-        cig += ops
-    seq = ''.join(r[9] for r in rows).encode()
-    qual = ''.join(r[10][:len(r[9])].ljust(len(r[9]), 'J') for r in rows).encode()
-    lens = [len(r[9]) for r in rows]
-    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]) if rows else []
-    ctx.rows_load(flag, ref, pos, cig_off, n_cig, cig or [0], np.frombuffer(seq, np.uint8),
-                  np.frombuffer(qual, np.uint8), offs, lens, units)
+    ctx.rows_load(*args)
     # reference span of a row <= read length + its deletions
-    dels = [sum(int(n) for n, op in re.findall(r'(\d+)([MIDNS])', r[5]) if op == 'D') for r in rows]
-    span = {id(r): len(r[9]) + d for r, d in zip(rows, dels)}
-    cap_lens = [max([int(r[3]) + span[id(r)] for p in pairs for r in p if r] + [8])
-                for _ in ref_names]
+    cap_lens = pileup_path_cases.span_cap_lens(ref_names, pairs)
     got_refmap, got_counts = _gpu_pileup_as_refmap(ctx, ref_names, cap_lens, quality_cutoff,
                                                    source=1)
     assert list(got_refmap) == list(want_refmap)

@@ -40,6 +40,22 @@ def test_version_and_errors(native):
     assert native.levenshtein('kitten', 'sitting') == 3
 
 
+def test_pileup_info_constants_without_context(native):
+    """mh_test_pileup_info with no context: the pileup's constants alone
+    (what tests/pileup_path_cases.py sizes its cases by), no launch shape."""
+    info = native.pileup_info()
+    assert set(info) == set(native.PILEUP_INFO_FIELDS) | {'win_len'}
+    assert info['max_ops'] == 128 and info['max_ins'] == 2 * info['max_ops']
+    assert info['xch_span'] % 64 == 0 and info['xch_span'] > 0
+    # DESIGN section 7: a pair of 1024-base reads always fits
+    assert info['ins_buf'] >= 3 * 1024
+    assert info['tok_lds_slots'] > 0 and info['tok_lds_keys'] > 0 and info['pileup_slack'] > 0
+    assert all(info[k] == 0 for k in native.PILEUP_INFO_FIELDS[7:])
+    assert info['win_len'] == []
+    with pytest.raises(native.NativeError):
+        native.check(native.lib().mh_test_pileup_info(None, None, 0, None), 'mh_test_pileup_info')
+
+
 def test_no_cpu_fallback_without_gpu(native):
     """On a host without a GPU the context refuses to start (no fallback)."""
     if native.device_count() > 0:
