@@ -328,6 +328,52 @@ int mh_pileup(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int32_t *
  * independently of the others, so theirs are the same. */
 int mh_pileup_only(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int32_t *ref_lens, int n_sel,
                    const int32_t *sel);
+/* Watched positions: the debug_reports of sam_to_conseqs (remap.py:169-225,
+ * 302-306).  Sets the (reference index, 1-based position) keys of the next
+ * mh_pileup calls, n_keys = 0 clears them; -3 above MH_WATCH_MAXKEYS keys or
+ * for a position < 1.  A watched pileup also fills, per key, a histogram of
+ * base (A C G T) x quality character (MH_WATCH_QBINS bins, ' ' .. '~') over
+ * the merged pairs that counted a base there, the quality being qual1's or
+ * qual2's as remap.py:305 picks it.  A key on a reference outside the
+ * pileup's n_refs, or past its counters, never counts.  mh_pileup_only with
+ * a selection refuses to run watched (-3). */
+#define MH_WATCH_MAXKEYS 1024
+#define MH_WATCH_QBINS 95
+int mh_pileup_watch(mh_ctx *ctx, int n_keys, const int32_t *refs, const int32_t *poss);
+/* The histogram of the last watched mh_pileup (remap.py:169-225, 302-306),
+ * keys in the caller's order: counts[n_keys][4][MH_WATCH_QBINS] and, per
+ * cell, the first matchmaker unit that added to it (INT64_MAX: none), which
+ * gives the insertion order of the reference's Counter. */
+int mh_pileup_watch_fetch(mh_ctx *ctx, uint32_t *counts, int64_t *first_unit);
+/* SAM text read as remap.matchmaker(samfile, include_singles=True) reads it
+ * (remap.py:853-889) and uploaded as rows, as mh_rows_load_csv does for
+ * prelim.csv: '@' lines are headers, every SN of an @SQ line (fields split
+ * at the first ':') names a reference; only '\n' is stripped; the first
+ * eleven tab fields are used; a row whose RNAME is no @SQ name is dropped;
+ * rows pair by QNAME, pairs in the order of their second rows, then the
+ * singles.  mh_sam_info gives the names and, per reference, the largest
+ * reference end (POS - 1 + M + D) of a mapped row. */
+int mh_rows_load_sam(mh_ctx *ctx, const char *text, int64_t len, int64_t *n_rows,
+                     int64_t *n_units, int32_t *n_refs, size_t *names_bytes);
+/* after mh_rows_load_sam: names '\n'-joined (names_bytes + 1 bytes), ends[n_refs] */
+int mh_sam_info(mh_ctx *ctx, char *names, size_t cap, int32_t *ends);
+/* Host-only parse of SAM text as mh_rows_load_sam parses it, no device: the
+ * sizes first (any array NULL), then the caller's arrays.  Per kept row:
+ * flag, reference index, POS, CIGAR ops ((len << 4) | op; an unmapped row
+ * has none, an invalid or over-long CIGAR is the single op 3) at cigar_off,
+ * SEQ / QUAL bytes (QUAL cut or padded with 'J' to SEQ's length) at
+ * seq_off; units as mh_rows_load takes them; names '\n'-joined.  Returns
+ * -3 (with a message) for a line with fewer than eleven fields or a FLAG /
+ * POS that is no integer, where the reference raises. */
+typedef struct {
+    int64_t n_rows, n_units, n_cigar, n_bases;
+    int32_t n_refs;
+    size_t names_bytes;
+} mh_sam_sizes;
+int mh_sam_parse(const char *text, int64_t len, mh_sam_sizes *sizes, int32_t *flag, int32_t *ref,
+                 int32_t *pos, int32_t *cigar_off, int32_t *n_cigar, uint32_t *cigar,
+                 int64_t *seq_off, int32_t *seq_len, uint8_t *seq, uint8_t *qual, int64_t *units,
+                 char *names, int32_t *ends);
 /* dense: n_refs x cap x 4 int32 counts of A,C,G,T at positions 1..cap;
  * nflag/dflag: n_refs x cap bytes ('N' seen -> count -1, '-' seen -> -2);
  * read_counts: merged pairs per ref; first_unit: first merged unit index

@@ -31,6 +31,7 @@
 #include "mh_fastq.h"
 #include "mh_gunzip.h"
 #include "mh_internal.h"
+#include "mh_sam.h"
 #include "mh_text.h"
 
 #include <map>
@@ -202,6 +203,8 @@ struct CtxEx : Ctx {
     std::vector<int32_t> csv_rows_info;   // per prelim.csv row: name id, flag, max M run, ref
     std::vector<int32_t> csv_present;     // compact ref id -> index into the @SQ list
     std::vector<std::string> csv_unknown; // names outside @SQ, by -1 - name id
+    std::vector<std::string> sam_names;   // mh_rows_load_sam: @SQ names in first-seen order
+    std::vector<int32_t> sam_ends;        // and each one's largest reference end
     int64_t fastq_lines1 = -1;            // newlines in FASTQ 1 (LineCounter, externals.py:206)
     DevIndex small;                       // reusable buffers of the non-cached (consensus) index
     // insertion tokens of the last pileup, aggregated: (ref, pos, token) -> count
@@ -788,6 +791,7 @@ int mh_ctx_destroy(mh_ctx *ctx)
     P.land_cap = 0;
     P.land_ok = false;
     hipFree(P.ins_scratch);
+    hipFree(P.watch_dpos); hipFree(P.watch_range); hipFree(P.watch_count); hipFree(P.watch_first);
     hipFree(P.sel);
     hipFree(P.win_map);
     for (auto &kv : c->len_tabs) hipFree(kv.second);
@@ -2401,6 +2405,105 @@ extern "C" int mh_rows_load_csv(mh_ctx *ctx, const char *text, int64_t len, int 
     return 0;
 }
 
+// SAM text (remap.py:853-889) -> rows; the references are the text's own
+// @SQ names, all of them (a pileup of these rows sizes its counters by them)
+extern "C" int mh_rows_load_sam(mh_ctx *ctx, const char *text, int64_t len, int64_t *n_rows,
+                                int64_t *n_units, int32_t *n_refs, size_t *names_bytes)
+{
+    if (!ctx || (!text && len > 0) || len < 0) return -3;
+    CtxEx *c = X(ctx);
+    SamRows R;
+    std::string err;
+    if (int st = sam_parse(text, len, R, err)) { set_error("%s", err.c_str()); return st; }
+    const uint32_t none = 0;
+    const uint8_t nob = 0;
+    int st = mh_rows_load(ctx, (int64_t)R.flag.size(), R.flag.data(), R.ref.data(), R.pos.data(),
+                          R.cig_off.data(), R.n_cigar.data(), R.cigar.empty() ? &none : R.cigar.data(),
+                          R.seq.empty() ? &nob : R.seq.data(), R.qual.empty() ? &nob : R.qual.data(),
+                          R.off.data(), R.len.data(), (int64_t)R.units.size() / 2, R.units.data());
+    if (st) return st;
+    // the prelim.csv bookkeeping describes other rows now
+    c->csv_rows_info.clear();
+    c->csv_present.clear();
+    c->csv_unknown.clear();
+    c->sam_names.swap(R.names);
+    c->sam_ends.swap(R.ends);
+    size_t nb = 0;
+    for (const std::string &n : c->sam_names) nb += n.size() + 1;
+    if (n_rows) *n_rows = (int64_t)R.flag.size();
+    if (n_units) *n_units = (int64_t)R.units.size() / 2;
+    if (n_refs) *n_refs = (int32_t)c->sam_names.size();
+    if (names_bytes) *names_bytes = nb;
+    return 0;
+}
+
+extern "C" int mh_sam_info(mh_ctx *ctx, char *names, size_t cap, int32_t *ends)
+{
+    if (!ctx) return -3;
+    CtxEx *c = X(ctx);
+    if (names) {
+        std::string all;
+        for (const std::string &n : c->sam_names) { all += n; all.push_back('\n'); }
+        if (all.size() + 1 > cap) { set_error("mh_sam_info: name buffer too small"); return -2; }
+        std::memcpy(names, all.c_str(), all.size() + 1);
+    }
+    if (ends && !c->sam_ends.empty())
+        std::memcpy(ends, c->sam_ends.data(), sizeof(int32_t) * c->sam_ends.size());
+    return 0;
+}
+
+// Watched positions of the next pileups (remap.py:169-225, 302-306): kept
+// sorted by (reference, position); run_pileup uploads them
+extern "C" int mh_pileup_watch(mh_ctx *ctx, int n_keys, const int32_t *refs, const int32_t *poss)
+{
+    if (!ctx || n_keys < 0 || (n_keys > 0 && (!refs || !poss))) return -3;
+    if (n_keys > MH_WATCH_MAXKEYS) {
+        set_error("mh_pileup_watch: %d keys (at most %d)", n_keys, MH_WATCH_MAXKEYS);
+        return -3;
+    }
+    for (int k = 0; k < n_keys; ++k)
+        if (poss[k] < 1) { set_error("mh_pileup_watch: key %d at position %d", k, poss[k]); return -3; }
+    PileState &P = X(ctx)->pile;
+    std::vector<int32_t> order((size_t)n_keys);
+    for (int k = 0; k < n_keys; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        return refs[a] != refs[b] ? refs[a] < refs[b] : poss[a] < poss[b];
+    });
+    P.watch_ref.resize((size_t)n_keys);
+    P.watch_pos.resize((size_t)n_keys);
+    for (int z = 0; z < n_keys; ++z) {
+        P.watch_ref[(size_t)z] = refs[order[(size_t)z]];
+        P.watch_pos[(size_t)z] = poss[order[(size_t)z]];
+    }
+    P.watch_order.swap(order);
+    return 0;
+}
+
+extern "C" int mh_pileup_watch_fetch(mh_ctx *ctx, uint32_t *counts, int64_t *first_unit)
+{
+    if (!ctx) return -3;
+    CtxEx *c = X(ctx);
+    PileState &P = c->pile;
+    const size_t nk = P.watch_order.size(), cells = 4 * (size_t)MH_WATCH_QBINS;
+    if (!nk) return 0;
+    if (!counts || !first_unit) return -3;
+    if (!P.watch_count || !P.watch_first) { set_error("no watched pileup (call mh_pileup)"); return -3; }
+    MH_HIP(hipSetDevice(c->device));
+    std::vector<uint32_t> cnt(nk * cells);
+    std::vector<uint64_t> fst(nk * cells);
+    MH_HIP(copy_sync(*c, cnt.data(), P.watch_count, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost));
+    MH_HIP(copy_sync(*c, fst.data(), P.watch_first, sizeof(uint64_t) * fst.size(), hipMemcpyDeviceToHost));
+    for (size_t z = 0; z < nk; ++z) {
+        const size_t k = (size_t)P.watch_order[z];
+        for (size_t x = 0; x < cells; ++x) {
+            counts[k * cells + x] = cnt[z * cells + x];
+            const uint64_t f = fst[z * cells + x];
+            first_unit[k * cells + x] = f > (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)f;
+        }
+    }
+    return 0;
+}
+
 extern "C" int mh_rows_info(mh_ctx *ctx, int32_t *out4, int32_t *present, char *unknown,
                             size_t cap)
 {
@@ -2460,6 +2563,11 @@ int mh_pileup_only(mh_ctx *ctx, int source, int q_cutoff, int n_refs, const int3
         for (int k = 0; k < n_sel; ++k) {
             if (sel[k] < 0 || sel[k] >= n_refs) { set_error("mh_pileup_only: reference %d out of range", sel[k]); return -3; }
             c->pile.only[(size_t)sel[k]] = 1;
+        }
+        if (!c->pile.watch_order.empty()) {
+            set_error("mh_pileup_only: watched positions are set (mh_pileup_watch); a watched pileup "
+                      "counts every reference");
+            return -3;
         }
     }
     int32_t cap = 1;

@@ -216,6 +216,16 @@ struct PileState {
     // references this pileup counts (mh_pileup_only; empty: all): the units
     // of any other are skipped and its counters stay zero
     std::vector<uint8_t> only;
+    // watched positions (mh_pileup_watch; remap.py:169-225, 302-306): the
+    // keys sorted by (reference, position), watch_order[z] = the caller's
+    // index of sorted key z; on the device their positions, the per-reference
+    // ranges of the pileup being run, and the histogram ([key][4][95] counts
+    // and first units) of the last watched pileup
+    std::vector<int32_t> watch_ref, watch_pos, watch_order;
+    int32_t *watch_dpos = nullptr, *watch_range = nullptr;
+    int watch_range_cap = 0;
+    uint32_t *watch_count = nullptr;
+    unsigned long long *watch_first = nullptr;
     int32_t *sel = nullptr;         // references of a multi-GPU exchange
     int sel_cap = 0;
     int32_t *win_map = nullptr;     // k_pileup: per reference (LDS window word offset, -1 none, -2 skipped; positions)

@@ -29,6 +29,9 @@ constexpr int PU_XCH = 5;        // 64-position chunks per mate expanded with al
 // exchange: any of them fails the pileup): a malformed row (CIGAR /
 // position); a unit whose merged insertions do not fit in PU_INSBUF
 constexpr unsigned long long PILE_ERR_ROW = 1, PILE_ERR_INSBUF = 2;
+// watched positions: quality characters ' ' (32, a deletion's placeholder)
+// to '~' (126), one bin each
+constexpr int PW_QBINS = MH_WATCH_QBINS, PW_Q0 = 32;
 
 struct RowV {
     int present, flag, ref, pos, n_cigar, rev, m;
@@ -77,6 +80,14 @@ struct PileArgs {
     int span_cap;                // reference span per mate staged in LDS
     int unit_bytes;              // staging bytes per wave
     char *ins_scratch;           // PU_INS_BYTES per wave of the grid
+    // watched positions (k_pileup<.., .., true> only; mh_pileup_watch): the
+    // keys' positions sorted by (reference, position), each reference's
+    // [first, end) range of them, and per key a [4][PW_QBINS] histogram of
+    // base x quality character with the first unit that added to each cell
+    const int32_t *watch_pos;
+    const int32_t *watch_range;  // [n_refs][2]
+    uint32_t *watch_count;
+    unsigned long long *watch_first;   // UINT64_MAX: never seen
 };
 
 template <int SRC>
@@ -295,7 +306,11 @@ __device__ __forceinline__ int wave_max_all(int v)
 // (pile_geometry); k_pileup<0> keeps 2 VGPRs in scratch (12 B per lane).
 // SKIP: some references are not counted (mh_pileup_only); a separate
 // instance, so the full pileup pays no per-unit LDS read or SGPR for it
-template <int SRC, bool SKIP>
+// WATCH: the debug report of remap.sam_to_conseqs (remap.py:169-225,
+// 302-306): a base counted at a watched (reference, position) also goes into
+// that key's base x quality histogram.  Separate instances again: the four
+// without it compile to what they were.
+template <int SRC, bool SKIP, bool WATCH>
 __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -746,6 +761,12 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
         // this reference's LDS counter window (wo < 0: none), wl positions
         const int wo = __builtin_amdgcn_readfirstlane(wmap[2 * ref]);
         const int wl = __builtin_amdgcn_readfirstlane(wmap[2 * ref + 1]);
+        // this reference's watched keys [wk0, wk1)
+        int wk0 = 0, wk1 = 0;
+        if constexpr (WATCH) {
+            wk0 = __builtin_amdgcn_readfirstlane(A.watch_range[2 * ref]);
+            wk1 = __builtin_amdgcn_readfirstlane(A.watch_range[2 * ref + 1]);
+        }
         // the merged character of position i (sam2aln merge_pairs, :192-237),
         // 0 past seq2; every LDS read unconditional (clamped index) so the two
         // positions of a round read together
@@ -781,6 +802,32 @@ __global__ __launch_bounds__(1024, 6) void k_pileup(PileArgs A)
             if (ok & isN) A.nflag[cell] = 1;
             if (ok & isD) A.dflag[cell] = 1;
             bool base = ok & !isN & !isD;
+            if constexpr (WATCH) {
+                // counts[nuc + q] of remap.py:302-306, under the base alone
+                // (also where the token below replaces it in the counters)
+                if (base && wk0 < wk1) {
+                    int lo_k = wk0, hi_k = wk1;   // first key at a position >= P
+                    while (lo_k < hi_k) {
+                        const int mid = (lo_k + hi_k) >> 1;
+                        if (A.watch_pos[mid] < P) lo_k = mid + 1; else hi_k = mid;
+                    }
+                    if (lo_k < wk1 && A.watch_pos[lo_k] == P) {
+                        // qual1[pos-1] if pos <= len(qual1) else qual2[pos-1]:
+                        // the padded qualities of mate index 0 / 1
+                        const int k = P <= lenA ? 0 : 1;
+                        const int j = P - 1 - pad(k);
+                        int q = -1;
+                        if (k < nm && j < len(k) - pad(k)) q = j < 0 ? '!' : (unsigned char)L.q(k)[j];
+                        const int code = (((int)mc >> 1) ^ ((int)mc >> 2)) & 3;
+                        if (q >= PW_Q0 && q < PW_Q0 + PW_QBINS)
+                            for (int z = lo_k; z < wk1 && A.watch_pos[z] == P; ++z) {
+                                const int64_t cell_w = ((int64_t)z * 4 + code) * PW_QBINS + (q - PW_Q0);
+                                atomicAdd(&A.watch_count[cell_w], 1u);
+                                atomicMin(&A.watch_first[cell_w], (unsigned long long)u);
+                            }
+                    }
+                }
+            }
             if (n_ins > 0) {
                 int hit = -1;   // keys are distinct and >= 1 (-1: no key)
                 hit = P == ik3 ? 3 : hit;
@@ -968,13 +1015,16 @@ static int pile_geometry(Ctx &c, int source, int64_t n_units, PileGeometry &g)
     // leaves at 16 (2 blocks of 12 waves: 8.0 -> 6.5 ms per C2 step).  LDS
     // per block is the windows plus the waves' staging areas.
     const int64_t lds0 = (int64_t)base + 4 * words;
-    const auto key = std::make_tuple(source, lds0, g.unit_bytes);
+    // the instance that will launch: the watching ones have their own resources
+    const bool watch = !P.watch_order.empty();
+    const auto key = std::make_tuple(source + (watch ? 2 : 0), lds0, g.unit_bytes);
     auto hit = P.shapes.find(key);
     if (hit == P.shapes.end()) {
         if (!c.n_cu) MH_HIP(hipDeviceGetAttribute(&c.n_cu, hipDeviceAttributeMultiprocessorCount, c.device));
         // the skipping instances have the same resources (the occupancy
         // query of the full ones stands for them)
-        const void *kern = source == 0 ? (const void *)k_pileup<0, false> : (const void *)k_pileup<1, false>;
+        const void *kern = watch ? (source == 0 ? (const void *)k_pileup<0, false, true> : (const void *)k_pileup<1, false, true>)
+                                 : (source == 0 ? (const void *)k_pileup<0, false, false> : (const void *)k_pileup<1, false, false>);
         MH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, PU_LDS));
         int best_w = 0, best_wpb = 1, best_nb = 1;
         for (int wpb = 16; wpb >= 1; --wpb) {
@@ -1042,8 +1092,44 @@ int run_pileup(Ctx &c, int source, int q_cutoff)
     if (P.n_refs > 0)
         MH_HIP(hipMemcpyAsync(P.win_map, geo.win_map.data(), sizeof(int32_t) * 2 * P.n_refs,
                               hipMemcpyHostToDevice, s));
+    // watched positions: the keys' positions and this pileup's per-reference
+    // ranges of them (a key on a reference >= n_refs is in no range)
+    const int n_watch = (int)P.watch_order.size();
+    const size_t watch_cells = (size_t)n_watch * 4 * PW_QBINS;
+    if (n_watch > 0) {
+        if (P.only.size() == (size_t)P.n_refs && P.n_refs > 0) {
+            set_error("mh_pileup: watched positions with a reference selection");
+            return -3;
+        }
+        if (!P.watch_dpos) {
+            MH_HIP(hipMalloc(&P.watch_dpos, sizeof(int32_t) * MH_WATCH_MAXKEYS));
+            MH_HIP(hipMalloc(&P.watch_count, sizeof(uint32_t) * MH_WATCH_MAXKEYS * 4 * PW_QBINS));
+            MH_HIP(hipMalloc(&P.watch_first, sizeof(unsigned long long) * MH_WATCH_MAXKEYS * 4 * PW_QBINS));
+        }
+        const int nr = P.n_refs > 0 ? P.n_refs : 1;
+        if (P.watch_range_cap < nr) {
+            hipFree(P.watch_range);
+            P.watch_range = nullptr;
+            P.watch_range_cap = 0;
+            MH_HIP(hipMalloc(&P.watch_range, sizeof(int32_t) * 2 * nr));
+            P.watch_range_cap = nr;
+        }
+        std::vector<int32_t> range(2 * (size_t)nr, 0);
+        for (int z = 0; z < n_watch; ++z) {
+            const int32_t r = P.watch_ref[(size_t)z];
+            if (r < 0 || r >= P.n_refs) continue;
+            if (range[2 * (size_t)r + 1] == 0) range[2 * (size_t)r] = z;
+            range[2 * (size_t)r + 1] = z + 1;
+        }
+        MH_HIP(copy_sync(c, P.watch_dpos, P.watch_pos.data(), sizeof(int32_t) * n_watch, hipMemcpyHostToDevice));
+        MH_HIP(copy_sync(c, P.watch_range, range.data(), sizeof(int32_t) * range.size(), hipMemcpyHostToDevice));
+    }
     const int64_t cells = (int64_t)P.n_refs * P.cap;
     for (int attempt = 0; attempt < 3; ++attempt) {
+        if (n_watch > 0) {   // every attempt counts from zero (a retried pass must not count twice)
+            MH_HIP(hipMemsetAsync(P.watch_count, 0, sizeof(uint32_t) * watch_cells, s));
+            MH_HIP(hipMemsetAsync(P.watch_first, 0xff, sizeof(unsigned long long) * watch_cells, s));
+        }
         MH_HIP(hipMemsetAsync(P.dense, 0, sizeof(int32_t) * 4 * (cells > 0 ? cells : 1), s));
         MH_HIP(hipMemsetAsync(P.nflag, 0, cells > 0 ? cells : 1, s));
         MH_HIP(hipMemsetAsync(P.dflag, 0, cells > 0 ? cells : 1, s));
@@ -1073,12 +1159,18 @@ int run_pileup(Ctx &c, int source, int q_cutoff)
         A.span_cap = geo.span;
         A.unit_bytes = geo.unit_bytes;
         A.ins_scratch = P.ins_scratch;
+        A.watch_pos = P.watch_dpos;
+        A.watch_range = P.watch_range;
+        A.watch_count = P.watch_count;
+        A.watch_first = P.watch_first;
         if (n_units > 0) {
             const int pk = prof_begin(c, "k_pileup");
             const bool skip = P.only.size() == (size_t)P.n_refs &&
                               std::find(P.only.begin(), P.only.end(), (uint8_t)0) != P.only.end();
-            const void *kern = source == 0 ? (skip ? (const void *)k_pileup<0, true> : (const void *)k_pileup<0, false>)
-                                           : (skip ? (const void *)k_pileup<1, true> : (const void *)k_pileup<1, false>);
+            const void *kern = source == 0 ? (skip ? (const void *)k_pileup<0, true, false> : (const void *)k_pileup<0, false, false>)
+                                           : (skip ? (const void *)k_pileup<1, true, false> : (const void *)k_pileup<1, false, false>);
+            if (n_watch > 0)
+                kern = source == 0 ? (const void *)k_pileup<0, false, true> : (const void *)k_pileup<1, false, true>;
             MH_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
             void *kargs[] = {&A};
             MH_HIP(hipLaunchKernel(kern, dim3((unsigned)geo.blocks), dim3(64 * geo.wpb), kargs, geo.lds, s));

@@ -98,6 +98,13 @@ def _declare(L):
                               ctypes.POINTER(ctypes.c_char_p), _I64P, _I64P, _I32P], ctypes.c_int),
         'mh_rows_info': ([_P, _P, _P, ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
         'mh_reads_fastq_lines': ([_P, _I64P], ctypes.c_int),
+        'mh_rows_load_sam': ([_P, ctypes.c_char_p, ctypes.c_int64, _I64P, _I64P, _I32P,
+                              ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_sam_info': ([_P, ctypes.c_char_p, ctypes.c_size_t, _P], ctypes.c_int),
+        'mh_sam_parse': ([ctypes.c_char_p, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                          _P, _P, ctypes.c_char_p, _P], ctypes.c_int),
+        'mh_pileup_watch': ([_P, ctypes.c_int, _P, _P], ctypes.c_int),
+        'mh_pileup_watch_fetch': ([_P, _P, _P], ctypes.c_int),
         'mh_pileup': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P], ctypes.c_int),
         'mh_pileup_only': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P], ctypes.c_int),
         'mh_pileup_dims': ([_P, ctypes.POINTER(ctypes.c_int), _I32P, _I64P, _I64P], ctypes.c_int),
@@ -314,6 +321,41 @@ def _ptr(a):
 PILEUP_INFO_FIELDS = ('xch_span', 'max_ops', 'ins_buf', 'max_ins', 'tok_lds_slots', 'tok_lds_keys',
                       'pileup_slack', 'blocks', 'wpb', 'win_words', 'n_units', 'tok_insert_blocks',
                       'tok_count_blocks', 'tok_events', 'tok_keys', 'n_refs')
+
+
+WATCH_MAXKEYS, WATCH_QBINS, WATCH_Q0 = 1024, 95, 32
+WATCH_NEVER = np.iinfo(np.int64).max
+
+
+class _SamSizes(ctypes.Structure):
+    _fields_ = [('n_rows', ctypes.c_int64), ('n_units', ctypes.c_int64), ('n_cigar', ctypes.c_int64),
+                ('n_bases', ctypes.c_int64), ('n_refs', ctypes.c_int32),
+                ('names_bytes', ctypes.c_size_t)]
+
+
+def sam_parse(text):
+    """mh_sam_parse: SAM text parsed on the host as mh_rows_load_sam parses it
+    (remap.py:853-889), no device.  Returns (names, ends, rows_load
+    arguments): the eleven arrays Context.rows_load takes."""
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    sz = _SamSizes()
+    none = [None] * 13
+    check(lib().mh_sam_parse(data, len(data), ctypes.byref(sz), *none), 'mh_sam_parse')
+    n, nc, nb = sz.n_rows, sz.n_cigar, sz.n_bases
+    i32 = lambda k: np.zeros(max(k, 1), dtype=np.int32)
+    flag, ref, pos, cig_off, n_cig, lens = (i32(n) for _ in range(6))
+    cigar = np.zeros(max(nc, 1), dtype=np.uint32)
+    offs = np.zeros(max(n, 1), dtype=np.int64)
+    seq, qual = np.zeros(max(nb, 1), dtype=np.uint8), np.zeros(max(nb, 1), dtype=np.uint8)
+    units = np.zeros(max(2 * sz.n_units, 1), dtype=np.int64)
+    ends = i32(sz.n_refs)
+    names = ctypes.create_string_buffer(sz.names_bytes + 1)
+    check(lib().mh_sam_parse(data, len(data), ctypes.byref(sz), _ptr(flag), _ptr(ref), _ptr(pos),
+                             _ptr(cig_off), _ptr(n_cig), _ptr(cigar), _ptr(offs), _ptr(lens),
+                             _ptr(seq), _ptr(qual), _ptr(units), names, _ptr(ends)), 'mh_sam_parse')
+    args = (flag[:n], ref[:n], pos[:n], cig_off[:n], n_cig[:n], cigar[:nc], seq[:nb], qual[:nb],
+            offs[:n], lens[:n], units[:2 * sz.n_units])
+    return names.value.decode().split('\n')[:-1], ends[:sz.n_refs], args
 
 
 def pileup_info(handle=None, n_refs=0):
@@ -1148,6 +1190,42 @@ class Context:
         unknown = buf.value.decode().split('\n')[:-1]
         return dict(n_rows=nr.value, n_units=nu.value, info=info[:nr.value],
                     present=present[:npres.value], unknown=unknown)
+
+    def rows_load_sam(self, text):
+        """SAM text -> device rows as remap.matchmaker(samfile,
+        include_singles=True) pairs them (remap.py:853-889).  Returns
+        dict(n_rows, n_units, names, ends): the @SQ names in first-seen
+        order and each one's largest reference end of a mapped row."""
+        data = text.encode() if isinstance(text, str) else bytes(text)
+        nr, nu, nrefs, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_size_t()
+        check(lib().mh_rows_load_sam(self.h, data, len(data), ctypes.byref(nr), ctypes.byref(nu),
+                                     ctypes.byref(nrefs), ctypes.byref(nb)), 'mh_rows_load_sam')
+        buf = ctypes.create_string_buffer(nb.value + 1)
+        ends = np.zeros(max(nrefs.value, 1), dtype=np.int32)
+        check(lib().mh_sam_info(self.h, buf, len(buf), _ptr(ends)), 'mh_sam_info')
+        return dict(n_rows=nr.value, n_units=nu.value, names=buf.value.decode().split('\n')[:-1],
+                    ends=ends[:nrefs.value])
+
+    def pileup_watch(self, keys):
+        """Watch the (reference index, 1-based position) keys in the next
+        pileups (the debug_reports of remap.py:169-225, 302-306); an empty
+        list stops watching."""
+        refs = np.ascontiguousarray([k[0] for k in keys], dtype=np.int32)
+        poss = np.ascontiguousarray([k[1] for k in keys], dtype=np.int32)
+        check(lib().mh_pileup_watch(self.h, len(refs), _ptr(refs) if len(refs) else None,
+                                    _ptr(poss) if len(poss) else None), 'mh_pileup_watch')
+        self._n_watch = len(refs)
+
+    def pileup_watch_fetch(self):
+        """(counts, first_unit) of the last watched pileup, [keys][4][95]:
+        base A C G T x quality character ' ' .. '~' (remap.py:169-225,
+        302-306); first_unit is WATCH_NEVER where nothing was counted."""
+        n = getattr(self, '_n_watch', 0)
+        counts = np.zeros((n, 4, WATCH_QBINS), dtype=np.uint32)
+        first = np.full((n, 4, WATCH_QBINS), WATCH_NEVER, dtype=np.int64)
+        if n:
+            check(lib().mh_pileup_watch_fetch(self.h, _ptr(counts), _ptr(first)), 'mh_pileup_watch_fetch')
+        return counts, first
 
     def fastq_lines(self):
         n = ctypes.c_int64()

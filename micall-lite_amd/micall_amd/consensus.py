@@ -425,6 +425,28 @@ def counts_to_conseqs_py(pile, order, seeds=None):
     return conseqs
 
 
+def format_debug_report(counts, first_unit):
+    """The report string of one watched position (remap.py:206-225) from its
+    [4][95] histogram of base x quality character and the first unit of
+    each cell (Context.pileup_watch_fetch): the Counter of nuc + quality in
+    the order its keys were first counted, then per quality, ascending,
+    'Q{nuc: n, ...}' over the cells of at least that quality, nucs in the
+    order they first appear among those cells, joined by ', '."""
+    codes, bins = np.nonzero(counts)
+    cells = sorted(zip(first_unit[codes, bins].tolist(), codes.tolist(), bins.tolist()))
+    seen = [('ACGT'[code], chr(_native.WATCH_Q0 + qbin), int(counts[code, qbin]))
+            for _first, code, qbin in cells]
+    mixtures = []
+    for min_quality in sorted(set(q for _nuc, q, _n in seen)):
+        filtered = Counter()
+        for nuc, q, n in seen:
+            if q >= min_quality:
+                filtered[nuc] += n
+        mixtures.append('{}{{{}}}'.format(min_quality, ', '.join(
+            '{}: {}'.format(nuc, n) for nuc, n in filtered.items())))
+    return ', '.join(mixtures)
+
+
 def extract_relevant_seed(aligned_conseq, aligned_seed):
     """remap.extract_relevant_seed (remap.py:129-138): the seed under the
     consensus from its first to its last non-gap column, gaps removed."""

@@ -152,6 +152,9 @@ class Shard:
         largest rank's size and all-gathered, then imported in rank order, so
         the token aggregation sees every rank's events.  No host objects are
         exchanged."""
+        if getattr(ctx, '_n_watch', 0):
+            raise RuntimeError('watched positions (Context.pileup_watch) are not exchanged between '
+                               'ranks: clear them before a sharded pileup')
         torch = self.torch
         dev = self.device
         if dev.type == 'cuda':

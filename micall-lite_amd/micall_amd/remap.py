@@ -27,7 +27,7 @@ import sys
 import numpy as np
 
 from . import _native, session, sharded_io
-from .consensus import Pileup, counts_to_conseqs
+from .consensus import Pileup, counts_to_conseqs, filter_conseqs, format_debug_report
 from .pipeline import CONSENSUS_Q_CUTOFF, RemapPipeline, write_remap_counts
 from .prelim_map import BOWTIE_THREADS, FIELDNAMES, READ_GAP_OPEN, REF_GAP_OPEN, check_fastq
 from .projects import ProjectConfig
@@ -98,6 +98,65 @@ def _write_unmapped(ctx, outs):
     for out, text in zip(outs, texts):
         if out is not None:
             out.write_bytes([text])
+
+
+def sam_to_conseqs(samfile, quality_cutoff=0, debug_reports=None, seeds=None, is_filtered=False,
+                   worker_pool=None, filter_coverage=1, distance_report=None):
+    """Consensus sequences of a SAM file's reads (remap.py:141-268), same
+    arguments and return value: {reference name: consensus} in the order the
+    references first received a merged pair.  The text is parsed and paired
+    on the host (mh_rows_load_sam), piled up on the device (mh_pileup, source
+    1) and, with seeds and is_filtered, filtered by distance to the seeds
+    there too (filter_conseqs).  worker_pool is accepted and not used.
+
+    debug_reports: a non-empty {(rname, pos): ...} gets every value replaced
+    by the reference's report of that position (remap.py:169-225, 302-306),
+    '' where nothing was counted; at most _native.WATCH_MAXKEYS keys.
+
+    Runs on this process's device alone, also in a sharded job.  The reads
+    and records resident from prelim_map() / remap() stay as they are: the
+    rows are a separate table of the context."""
+    session.shard()                  # in a sharded job torch's runtime comes up first
+    ctx = session.context()
+    rows = ctx.rows_load_sam(samfile.read())
+    names = rows['names']
+    index = {name: r for r, name in enumerate(names)}
+    ref_lens = [max(1, int(end), len(seeds.get(name, '')) if seeds else 0)
+                for name, end in zip(names, rows['ends'])]
+    keys = []
+    if debug_reports:
+        # a key that can never match (unknown name, no position) reports ''
+        keys = [key for key in debug_reports
+                if key[0] in index and isinstance(key[1], int) and key[1] >= 1]
+    ctx.pileup_watch([(index[rname], pos) for rname, pos in keys])
+    try:
+        ctx.pileup(1, quality_cutoff, ref_lens)
+        watched = ctx.pileup_watch_fetch() if keys else None
+    finally:
+        ctx.pileup_watch([])
+    pile = Pileup(ctx.pileup_fetch(), names)
+    order = pile.refs_with_reads()
+    if seeds:
+        for r in order:
+            seeds[names[r]]          # the reference's KeyError (remap.py:196)
+    if debug_reports:
+        for key in debug_reports:
+            debug_reports[key] = ''
+        for k, key in enumerate(keys):
+            debug_reports[key] = format_debug_report(watched[0][k], watched[1][k])
+    new_conseqs = counts_to_conseqs(pile, order, seeds=seeds)
+    if not (seeds and is_filtered) or len(new_conseqs) < 2:
+        return new_conseqs
+    return filter_conseqs(ctx, pile, order, new_conseqs, seeds, filter_coverage, distance_report)
+
+
+def build_conseqs(samfilename, seeds=None, is_filtered=False, worker_pool=None, filter_coverage=1,
+                  distance_report=None):
+    """sam_to_conseqs of a SAM file at CONSENSUS_Q_CUTOFF (remap.py:336-370)."""
+    with open(samfilename, 'r') as samfile:
+        return sam_to_conseqs(samfile, CONSENSUS_Q_CUTOFF, seeds=seeds, is_filtered=is_filtered,
+                              worker_pool=worker_pool, filter_coverage=filter_coverage,
+                              distance_report=distance_report)
 
 
 class RemapRun(RemapPipeline):
@@ -224,9 +283,11 @@ def remap(fastq1, fastq2, prelim_csv, remap_csv, remap_counts_csv=None, remap_co
           count_threshold=10, rdgopen=READ_GAP_OPEN, rfgopen=REF_GAP_OPEN, stderr=sys.stderr,
           gzip=False, debug_file_prefix=None, keep=False, json=None):
     """Iterative re-mapping against the sample's own consensus sequences
-    (remap.py:381-658).  bt2_path, bt2build_path, nthreads, stderr, gzip and
-    debug_file_prefix are accepted for the signature and not used; keep
-    writes the last consensus FASTA (there are no other temp files)."""
+    (remap.py:381-658).  bt2_path, bt2build_path, nthreads, stderr and gzip
+    are accepted for the signature and not used; keep writes the last
+    consensus FASTA (there are no other temp files).  debug_file_prefix P
+    leaves P_remap<n>_debug_ref.fasta and P_remap<n>_debug.sam for every pass
+    n of the loop, as the reference does (remap.py:560-571, 758-760)."""
     check_fastq(fastq1, fastq2)
     rdgopen = READ_GAP_OPEN if rdgopen is None else int(rdgopen)
     rfgopen = REF_GAP_OPEN if rfgopen is None else int(rfgopen)
@@ -263,8 +324,13 @@ def remap(fastq1, fastq2, prelim_csv, remap_csv, remap_counts_csv=None, remap_co
         if handle and writer and conseqs:
             handle.seek(0)
             handle.truncate()
+    after_pass = None
+    if debug_file_prefix is not None:
+        def after_pass():
+            _write_debug_files(ctx, run, '{}_remap{}'.format(debug_file_prefix, len(run.pass_refs)), sh)
     conseqs, new_counts, unmapped_count = run.iterate(conseqs, map_counts, raw_count,
-                                                      remap_counts_writer=counts_out)
+                                                      remap_counts_writer=counts_out,
+                                                      after_pass=after_pass)
     if writer:
         csv.DictWriter(remap_csv, FIELDNAMES, lineterminator=os.linesep).writeheader()
     run.rows_are_records = False
@@ -304,6 +370,36 @@ def remap(fastq1, fastq2, prelim_csv, remap_csv, remap_counts_csv=None, remap_co
         # re-mapping's single reference included (remap.py:624-630, 689-692)
         with open(os.path.join(work_path, 'temp.fasta'), 'w') as f:
             f.writelines('>%s\n%s\n' % item for item in last.items())
+
+
+def _write_debug_files(ctx, run, prefix, shard=None):
+    """The copies map_to_reference leaves of one pass (remap.py:758-760): the
+    FASTA of the sequences mapped to (remap.py:689-692) and the SAM file, its
+    three header lines (remap.py:728-731) and every read's line in input
+    order.  Sharded: rank 0 writes the FASTA and the header, every rank its
+    own lines after them (SharedOutput, as remap.csv's rows)."""
+    refseqs = run.last_refseqs
+    sam_path = prefix + '_debug.sam'
+    if session.is_writer():
+        with open(prefix + '_debug_ref.fasta', 'w') as f:
+            f.writelines('>%s\n%s\n' % item for item in refseqs.items())
+        sam = open(sam_path, 'w')
+        sam.write('@HD\tVN:1.0\tSO:unsorted\n')
+        sam.writelines('@SQ\tSN:%s\tLN:%d\n' % (name, len(seq)) for name, seq in refseqs.items())
+        sam.write('@PG\tID:bowtie2\tPN:bowtie2\tVN:2.2.3\tCL:""\n')
+        sam.flush()
+    if shard is not None:
+        shard.barrier()              # the file exists, with its header
+        if not session.is_writer():
+            sam = open(sam_path, 'r+')
+    try:
+        out = sharded_io.SharedOutput(shard, sam)
+        out.write_rows(ctx, 0, None, [0, ctx.reads_count()[0]])
+        if shard is not None:
+            shard.barrier()
+        out.finish()
+    finally:
+        sam.close()
 
 
 def _write_final_counts(writer, new_counts, unmapped_count):
