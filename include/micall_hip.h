@@ -40,7 +40,8 @@
  *      SequenceReport._count_reads (micall/core/aln2counts.py:115-172) and
  *      InsertionWriter.write (:748-811)
  *          -> mh_a2c_load_csv / mh_a2c_load_rows, mh_a2c_counts,
- *             mh_a2c_inserts.
+ *             mh_a2c_inserts; the nucleotide variants of the coordinate
+ *             regions (:346-375, :537-549) -> mh_a2c_variants.
  *
  * Conventions: every function returns 0 on success, -1 on traceback failure
  * (mh_gotoh_align only), -2 on out-of-memory, -3 on a bad argument, -4 on a
@@ -656,6 +657,35 @@ int mh_a2c_insert_rows(mh_ctx *ctx, int slot, const char *lead, int n_ranges, co
  * mh_a2c_load_resident: [0] the row order (when not built yet) + staging
  * (k_a2c_stage), [1] the bin lists + k_a2c_count + fetch. */
 int mh_a2c_timing(mh_ctx *ctx, int slot, double *ms3);
+/* The nucleotide variants of n_regions coordinate regions over the rows of
+ * group g (the loop of aln2counts.py:346-375 and the report of :537-549): per
+ * region k and row, clipped = ('-' * offset + seq)[start[k]:end[k]] (Python
+ * slice rules) counts when twice its bytes other than '-' exceed ref_len[k];
+ * equal clipped sequences (byte identity, the length included) add their
+ * counts up (64-bit), and the region keeps its max_variants[k] greatest by
+ * (count, sequence as bytes).  A region with max_variants 0 costs no device
+ * work.  The cut, ties in count included, is decided on the device: besides
+ * fixed-size records only the kept sequences' text comes to the host.
+ * key_bits (8..64) = hash bits used as the grouping key: 64 in the product;
+ * a small value makes distinct sequences share a key, which every call
+ * detects (each row's window is compared with its entry's first row's) and
+ * reports as -4 "variant hash collision", never as a merged count.
+ * n_kept[k] (may be NULL) = entries kept for region k.  -3: a negative
+ * window, reference length or cut, n_regions < 1, key_bits outside 8..64. */
+int mh_a2c_variants(mh_ctx *ctx, int slot, int64_t g, int n_regions, const int64_t *start,
+                    const int64_t *end, const int64_t *ref_len, const int64_t *max_variants,
+                    int key_bits, int64_t *n_kept);
+/* The kept entries of the last mh_a2c_variants in report order (region index,
+ * then count and sequence descending): region, count, len per entry, and the
+ * sequences back to back (padding '-' materialised) in seqs.  seqs NULL:
+ * *used = bytes needed. */
+int mh_a2c_variant_entries(mh_ctx *ctx, int slot, int32_t *region, int64_t *count, int32_t *len,
+                           char *seqs, size_t cap, size_t *used);
+/* Of the last mh_a2c_variants: stats4 = (region, row) pairs that counted,
+ * distinct entries, entries sharing the last kept count of a region whose cut
+ * left some of them out, bytes of sequence text copied to the host; *ms (may
+ * be NULL) = host wall ms of the call, device work included. */
+int mh_a2c_variant_stats(mh_ctx *ctx, int slot, int64_t *stats4, double *ms);
 
 /* ---- aln2counts counting split over the ranks of a job (the same
  * aln2counts.py:115-172 loops; the counters are sums and a first row is a

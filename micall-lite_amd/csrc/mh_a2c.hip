@@ -30,6 +30,12 @@
 //                 table (count, first row), every member is compared with
 //                 its group's first row (a collision is an error, never a
 //                 merge) and the distinct strings are gathered for the host.
+//   k_a2c_var_*   the nucleotide variants of the coordinate regions (the loop
+//                 of :346-375, the report of :537-549): per (region, row) the
+//                 padded row clipped to the region's window, equal clipped
+//                 sequences grouped the same way, and each region's greatest
+//                 by (count, sequence) picked on the device (see the section
+//                 at the end of this file).
 // Host half (below the kernels): aligned.csv as csv.DictReader reads it,
 // consecutive (refname, qcut) groups (itertools.groupby, :884-887), the
 // codon extent of every frame, the bin lists.
@@ -88,6 +94,15 @@ struct A2CEntry {
     unsigned long long count;
 };
 
+// One distinct clipped sequence of a coordinate region (mh_a2c_variants).
+struct A2CVarEntry {
+    int32_t region;    // index among the call's regions with a cut above 0
+    uint32_t first;    // first row of the group (0-based) that read it
+    int32_t len;       // bytes of the clipped sequence
+    int32_t pad;
+    unsigned long long count;
+};
+
 struct A2CState {
     // host
     int64_t n_rows = 0, n_bins = 0;
@@ -117,6 +132,12 @@ struct A2CState {
     std::string aminos;                       // one line per entry
     std::string ins_rows;                     // mh_a2c_insert_rows text (size query, then copy)
     std::unordered_map<const void *, size_t> dcap;   // bytes behind each device pointer (grow-only)
+    // kept variants of the last mh_a2c_variants, in report order
+    std::vector<A2CVarEntry> var_entries;
+    std::vector<int32_t> var_region;          // the caller's region index of each
+    std::string var_text;                     // their clipped sequences, back to back
+    int64_t var_stats[4] = {0, 0, 0, 0};      // pairs kept, entries, tied at a cut, text bytes fetched
+    double t_var = 0;
     double t_parse = 0, t_count = 0, t_ins = 0;
     // a part of aligned.csv held between mh_a2c_part_open and _count (mapped)
     const char *part_text = nullptr;          // (null for an empty file)
@@ -971,6 +992,9 @@ static void a2c_clear_inserts(A2CState &S)
 {
     S.entries.clear();
     S.aminos.clear();
+    S.var_entries.clear();
+    S.var_region.clear();
+    S.var_text.clear();
 }
 
 }  // namespace mh
@@ -1811,5 +1835,621 @@ extern "C" int mh_a2c_insert_merge(mh_ctx *ctx, int slot, const uint8_t *buf, in
         S.aminos.push_back('\n');
     }
     if (n_entries) *n_entries = (int64_t)S.entries.size();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Nucleotide variants of the coordinate regions of one run: the loop
+// SequenceReport.read runs per region over every row (aln2counts.py:346-375)
+// and the report write_nuc_variants (:537-549) was meant to write.  Per
+// (region, row) the row padded with '-' to its offset is clipped to the
+// region's window [start, end) (Python slice rules), kept when twice its
+// bytes other than '-' exceed the coordinate reference's length, and equal
+// clipped sequences (byte identity, the length included) add their counts up.
+// A region's report is its max_variants largest by (count, sequence).
+//   k_a2c_var_hash     a wavefront per pair: the lanes stride the window 64
+//                      bytes at a time (the padding is synthesised), each
+//                      keeps the sum of a per-(position, byte) mix and the
+//                      wave adds the sums up; the length and the region go
+//                      into the key.  A pair whose row cannot hold enough
+//                      bytes of the window is rejected before any is read.
+//   k_a2c_var_count    a thread per pair: equal keys of a wave are combined
+//                      (the dominant variant is most of every wave) before one
+//                      lane claims / finds the slot and adds count and first
+//                      row, as k_a2c_ins_count does per thread.
+//   k_a2c_var_verify   a wavefront per pair: its window against the window
+//                      of its entry's first row, byte for byte; a mismatch is
+//                      an error of the call, never a merged count.
+//   k_a2c_var_compact  the occupied slots as entries.
+//   k_a2c_var_select   a block per (slice of entries, region), max_variants
+//                      rounds: the largest count among the entries not kept
+//                      yet, then among the entries tied at it the greatest
+//                      sequence by successive 8-byte big-endian chunks (bytes
+//                      past the end are 0, so a proper prefix sorts below the
+//                      longer one).  A region's greatest entries are among
+//                      its slices' greatest, so a second launch of a block
+//                      per region picks from those.  The cut, ties included,
+//                      is decided here: only fixed-size records of the kept
+//                      entries go to the host.
+//   k_a2c_var_tied     how many entries share a region's last kept count (the
+//                      "tied at the cut" figure of the stats).
+//   k_a2c_var_gather   the text of the kept entries, padding materialised.
+// ---------------------------------------------------------------------------
+namespace mh {
+
+constexpr int A2C_VAR_COMBINE = 4;       // rounds of equal-key combining in a wave
+constexpr int A2C_VAR_SLICE = 2048;      // entries a block of the first selection level takes
+
+struct A2CVarArgs {
+    const uint8_t *text;
+    const A2CRow *rows;          // the rows of one group
+    const int64_t *win;          // per region: start, end, reference length, max_variants
+    int64_t n_rows, n_pairs;
+    int key_bits;
+    uint64_t *h;                 // per (region, row): 0 = does not count
+    uint64_t *tkey;
+    unsigned long long *tcnt;
+    uint32_t *tfirst;
+    int32_t *tregion;
+    uint64_t mask;
+    A2CVarEntry *entries;
+    unsigned long long *ctr;     // [0] pairs that count, [1] mismatches, [2] entries
+};
+
+// clipped = ('-' * off + seq)[start:end]: padded positions [lo, hi)
+__device__ __forceinline__ void a2c_var_clip(const A2CRow &R, int64_t start, int64_t end,
+                                             int64_t &lo, int64_t &hi)
+{
+    const int64_t L = (int64_t)R.off + R.len;
+    lo = start < L ? start : L;
+    hi = end < L ? end : L;
+    if (hi < lo) hi = lo;
+}
+
+// the byte at padded position pos < off + len
+__device__ __forceinline__ uint32_t a2c_var_byte(const uint8_t *text, const A2CRow &R, int64_t pos)
+{
+    return pos < R.off ? (uint32_t)'-' : (uint32_t)text[R.soff + (pos - R.off)];
+}
+
+__device__ __forceinline__ uint64_t a2c_var_slot(uint64_t h, uint64_t mask)
+{
+    return ((h * 0x9e3779b97f4a7c15ull) >> 20) & mask;
+}
+
+__device__ __forceinline__ unsigned long long a2c_wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_a2c_var_hash(A2CVarArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    unsigned long long kept = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < A.n_pairs; p += n_waves) {
+        const int rg = (int)(p / A.n_rows);
+        const A2CRow R = A.rows[p % A.n_rows];
+        const int64_t *w = A.win + 4 * rg;
+        int64_t lo, hi;
+        a2c_var_clip(R, w[0], w[1], lo, hi);
+        const int64_t rlo = lo > R.off ? lo : R.off;     // the read's own bytes: [rlo, hi)
+        uint64_t key = 0;
+        if (2 * (hi - rlo) > w[2]) {
+            uint64_t part = 0;
+            int64_t bases = 0;
+            for (int64_t q0 = lo; q0 < hi; q0 += 64) {
+                const int64_t q = q0 + lane;
+                const bool in = q < hi;
+                const uint32_t ch = in ? a2c_var_byte(A.text, R, q) : (uint32_t)'-';
+                if (in) part += a2c_mix(((uint64_t)(q - lo) << 8) | ch);
+                bases += __popcll(__ballot(in && ch != (uint32_t)'-'));
+            }
+            if (2 * bases > w[2]) {
+                part = a2c_wave_sum(part);
+                const uint64_t h = a2c_mix(part ^ a2c_mix(((uint64_t)(hi - lo) << 20) ^ (uint64_t)rg));
+                key = A.key_bits >= 64 ? (h | 1ull) : (((h & ((1ull << A.key_bits) - 1)) << 1) | 1ull);
+                ++kept;
+            }
+        }
+        if (lane == 0) A.h[p] = key;
+    }
+    if (lane == 0 && kept) atomicAdd(&A.ctr[0], kept);
+}
+
+__device__ void a2c_var_add(const A2CVarArgs &A, uint64_t h, int rg, unsigned long long cnt, uint32_t first)
+{
+    uint64_t s = a2c_var_slot(h, A.mask);
+    for (;;) {
+        const unsigned long long old =
+            atomicCAS((unsigned long long *)&A.tkey[s], 0ull, (unsigned long long)h);
+        if (old == 0ull || old == h) {
+            if (old == 0ull) A.tregion[s] = rg;
+            atomicAdd(&A.tcnt[s], cnt);
+            atomicMin(&A.tfirst[s], first);
+            return;
+        }
+        s = (s + 1) & A.mask;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_a2c_var_count(A2CVarArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t h = 0;
+    uint32_t idx = 0;
+    unsigned long long cnt = 0;
+    int rg = 0;
+    if (p < A.n_pairs) {
+        h = A.h[p];
+        idx = (uint32_t)(p % A.n_rows);
+        rg = (int)(p / A.n_rows);
+        if (h) cnt = A.rows[idx].cnt;
+    }
+    bool todo = h != 0;
+    for (int round = 0; round < A2C_VAR_COMBINE; ++round) {
+        const unsigned long long act = __ballot(todo);
+        if (!act) break;
+        const int leader = __ffsll((long long)act) - 1;
+        const uint64_t k = __shfl((unsigned long long)h, leader);
+        const bool mine = todo && h == k;
+        const unsigned long long sum = a2c_wave_sum(mine ? cnt : 0ull);
+        uint32_t mn = mine ? idx : A2C_NONE;
+#pragma unroll
+        for (int d = 32; d; d >>= 1) {
+            const uint32_t o = __shfl_xor(mn, d);
+            mn = o < mn ? o : mn;
+        }
+        if (lane == leader) a2c_var_add(A, h, rg, sum, mn);
+        todo = todo && !mine;
+    }
+    if (todo) a2c_var_add(A, h, rg, cnt, idx);
+}
+
+__global__ __launch_bounds__(256) void k_a2c_var_verify(A2CVarArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    unsigned long long wrong = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); p < A.n_pairs; p += n_waves) {
+        const uint64_t h = A.h[p];
+        if (!h) continue;
+        const int rg = (int)(p / A.n_rows);
+        const uint32_t idx = (uint32_t)(p % A.n_rows);
+        uint64_t s = a2c_var_slot(h, A.mask);
+        while (A.tkey[s] != h) s = (s + 1) & A.mask;
+        const uint32_t fidx = A.tfirst[s];
+        bool bad = A.tregion[s] != rg;
+        if (!bad && fidx != idx) {
+            const A2CRow R = A.rows[idx], F = A.rows[fidx];
+            const int64_t *w = A.win + 4 * rg;
+            int64_t lo, hi, flo, fhi;
+            a2c_var_clip(R, w[0], w[1], lo, hi);
+            a2c_var_clip(F, w[0], w[1], flo, fhi);
+            bad = hi - lo != fhi - flo;
+            if (!bad)
+                for (int64_t i = lane; i < hi - lo; i += 64)
+                    bad = bad || a2c_var_byte(A.text, R, lo + i) != a2c_var_byte(A.text, F, flo + i);
+        }
+        if (__any(bad)) ++wrong;
+    }
+    if (lane == 0 && wrong) atomicAdd(&A.ctr[1], wrong);
+}
+
+__global__ __launch_bounds__(256) void k_a2c_var_compact(A2CVarArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool used = s <= A.mask && A.tkey[s] != 0;
+    const unsigned long long b = __ballot(used);
+    if (!b) return;
+    unsigned long long base = 0;
+    const int leader = __ffsll((long long)b) - 1;
+    if (lane == leader) base = atomicAdd(&A.ctr[2], (unsigned long long)__popcll(b));
+    base = __shfl(base, leader);
+    if (!used) return;
+    A2CVarEntry e;
+    e.region = A.tregion[s];
+    e.first = A.tfirst[s];
+    e.count = A.tcnt[s];
+    e.pad = 0;
+    int64_t lo, hi;
+    a2c_var_clip(A.rows[e.first], A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
+    e.len = (int32_t)(hi - lo);
+    A.entries[base + __popcll(b & ((1ull << lane) - 1))] = e;
+}
+
+// bytes [j, j + 8) of an entry's clipped sequence, big-endian, 0 past its end
+__device__ uint64_t a2c_var_chunk(const A2CVarArgs &A, const A2CVarEntry &e, int64_t j)
+{
+    const A2CRow F = A.rows[e.first];
+    int64_t lo, hi;
+    a2c_var_clip(F, A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
+    uint64_t key = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        key = (key << 8) | (j + b < e.len ? (uint64_t)a2c_var_byte(A.text, F, lo + j + b) : 0ull);
+    return key;
+}
+
+// The greatest entries of region blockIdx.y among src[b0, b1), in order, into
+// out + slot * cap (slot = region * gridDim.x + blockIdx.x), at most
+// min(max_variants, cap) of them.  Two levels: every slice of A2C_VAR_SLICE
+// entries keeps its own greatest (gridDim.x slices, seg_stride 0); the
+// region's greatest are among those, so one block per region then picks from
+// the slices' picks (gridDim.x 1, the region's segment of seg_stride
+// entries; unused places hold region -1).  state per entry: 0 free, 1 kept,
+// 2 tied at the round's count and still the greatest on every chunk compared.
+__global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2CVarEntry *src, int64_t n_src,
+                                                         int64_t slice, int64_t seg_stride, uint8_t *state,
+                                                         int64_t cap, A2CVarEntry *out, int32_t *n_out,
+                                                         unsigned long long *last_out)
+{
+    __shared__ unsigned long long s_best, s_key;
+    __shared__ unsigned int s_has, s_alive, s_pick;
+    const int rg = blockIdx.y, tid = threadIdx.x;
+    const int64_t b0 = (int64_t)rg * seg_stride + (int64_t)blockIdx.x * slice;
+    const int64_t b1 = b0 + slice < n_src ? b0 + slice : n_src;
+    const int64_t slot = (int64_t)rg * gridDim.x + blockIdx.x;
+    const int64_t m = A.win[4 * rg + 3] < cap ? A.win[4 * rg + 3] : cap;
+    int64_t got = 0;
+    unsigned long long last = 0;
+    for (; got < m; ++got) {
+        if (tid == 0) { s_best = 0; s_has = 0; s_alive = 0; }
+        __syncthreads();
+        unsigned long long best = 0;
+        bool has = false;
+        for (int64_t e = b0 + tid; e < b1; e += 1024)
+            if (src[e].region == rg && state[e] != 1) {
+                has = true;
+                best = src[e].count > best ? src[e].count : best;
+            }
+        if (has) {
+            atomicMax(&s_best, best);
+            s_has = 1;
+        }
+        __syncthreads();
+        if (!s_has) break;
+        best = s_best;
+        unsigned int n = 0;
+        for (int64_t e = b0 + tid; e < b1; e += 1024)
+            if (src[e].region == rg && state[e] != 1) {
+                const bool tied = src[e].count == best;
+                state[e] = tied ? 2 : 0;
+                n += tied;
+            }
+        if (n) atomicAdd(&s_alive, n);
+        __syncthreads();
+        unsigned int alive = s_alive;
+        for (int64_t j = 0; alive > 1; j += 8) {
+            __syncthreads();
+            if (tid == 0) { s_key = 0; s_alive = 0; }
+            __syncthreads();
+            unsigned long long top = 0;
+            for (int64_t e = b0 + tid; e < b1; e += 1024)
+                if (state[e] == 2 && src[e].region == rg) {
+                    const unsigned long long k = a2c_var_chunk(A, src[e], j);
+                    top = k > top ? k : top;
+                }
+            if (top) atomicMax(&s_key, top);
+            __syncthreads();
+            top = s_key;
+            n = 0;
+            for (int64_t e = b0 + tid; e < b1; e += 1024)
+                if (state[e] == 2 && src[e].region == rg) {
+                    if (a2c_var_chunk(A, src[e], j) == top) ++n;
+                    else state[e] = 0;
+                }
+            if (n) atomicAdd(&s_alive, n);
+            __syncthreads();
+            alive = s_alive;
+            if (top == 0) break;      // every one ended: equal sequences (one entry each: not reached)
+        }
+        __syncthreads();
+        if (tid == 0) s_pick = 0xffffffffu;
+        __syncthreads();
+        for (int64_t e = b0 + tid; e < b1; e += 1024)
+            if (state[e] == 2 && src[e].region == rg) atomicMin(&s_pick, (unsigned int)(e - b0));
+        __syncthreads();
+        const int64_t pick = b0 + s_pick;
+        for (int64_t e = b0 + tid; e < b1; e += 1024)
+            if (state[e] == 2 && src[e].region == rg) state[e] = e == pick ? 1 : 0;
+        if (tid == 0) out[slot * cap + got] = src[pick];
+        last = best;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        n_out[slot] = (int32_t)got;
+        last_out[slot] = last;
+    }
+}
+
+// eq[region] = entries of the region whose count is last[region] (the count
+// of its last kept entry): more of them than were kept means the cut fell
+// inside a tie.  One atomic per wave and region met.
+__global__ __launch_bounds__(256) void k_a2c_var_tied(A2CVarArgs A, int64_t n_ent,
+                                                      const unsigned long long *last,
+                                                      unsigned long long *eq)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int rg = -1;
+    if (e < n_ent && A.entries[e].count == last[A.entries[e].region]) rg = A.entries[e].region;
+    for (;;) {
+        const unsigned long long act = __ballot(rg >= 0);
+        if (!act) break;
+        const int leader = __ffsll((long long)act) - 1;
+        const int r = __shfl(rg, leader);
+        const unsigned long long same = __ballot(rg == r);
+        if (lane == leader) atomicAdd(&eq[r], (unsigned long long)__popcll(same));
+        if (rg == r) rg = -1;
+    }
+}
+
+// a wavefront per kept entry: its clipped sequence at out + off[k]
+__global__ __launch_bounds__(256) void k_a2c_var_gather(A2CVarArgs A, const A2CVarEntry *kept,
+                                                        const int64_t *off, int64_t n, char *out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n) return;
+    const A2CVarEntry e = kept[k];
+    const A2CRow F = A.rows[e.first];
+    int64_t lo, hi;
+    a2c_var_clip(F, A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
+    for (int64_t i = lane; i < e.len; i += 64) out[off[k] + i] = (char)a2c_var_byte(A.text, F, lo + i);
+}
+
+}  // namespace mh
+
+extern "C" int mh_a2c_variants(mh_ctx *ctx, int slot, int64_t g, int n_regions, const int64_t *start,
+                               const int64_t *end, const int64_t *ref_len, const int64_t *max_variants,
+                               int key_bits, int64_t *n_kept)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || n_regions < 1 || !start || !end || !ref_len ||
+        !max_variants || key_bits < 8 || key_bits > 64)
+        return -3;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    A2CState &S = *a2c_state(c, slot);
+    S.var_entries.clear();
+    S.var_region.clear();
+    S.var_text.clear();
+    for (int k = 0; k < 4; ++k) S.var_stats[k] = 0;
+    S.t_var = 0;
+    const int64_t ng = (int64_t)S.g_first.size() - 1;
+    if (g < 0 || g >= ng) { set_error("mh_a2c_variants: no group %lld", (long long)g); return -3; }
+    std::vector<int64_t> win;       // the regions with a cut above 0
+    std::vector<int32_t> which;
+    for (int k = 0; k < n_regions; ++k) {
+        if (start[k] < 0 || end[k] < 0 || ref_len[k] < 0 || max_variants[k] < 0 ||
+            start[k] > 4 * A2C_MAX_SPAN || end[k] > 4 * A2C_MAX_SPAN) {
+            set_error("mh_a2c_variants: bad window %lld..%lld of region %d", (long long)start[k],
+                      (long long)end[k], k);
+            return -3;
+        }
+        if (n_kept) n_kept[k] = 0;
+        if (max_variants[k] == 0) continue;
+        which.push_back(k);
+        win.insert(win.end(), {start[k], end[k], ref_len[k], max_variants[k]});
+    }
+    const int na = (int)which.size();
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * na;
+    if (np == 0) return 0;
+    if (np >= (int64_t)1 << 32) { set_error("mh_a2c_variants: more than 2**32 (region, row) pairs"); return -3; }
+    auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s = c.stream;
+    int64_t *d_win = nullptr, *d_toff = nullptr;
+    uint64_t *d_h = nullptr, *d_tkey = nullptr;
+    unsigned long long *d_tcnt = nullptr, *d_ctr = nullptr, *d_last = nullptr;
+    uint32_t *d_tfirst = nullptr;
+    int32_t *d_tregion = nullptr, *d_nkept = nullptr;
+    A2CVarEntry *d_ent = nullptr, *d_kept = nullptr, *d_cand = nullptr;
+    uint8_t *d_state = nullptr;
+    char *d_out = nullptr;
+    int rc = 0;
+    A2CVarArgs a{};
+    uint64_t tsize = 1024;
+    unsigned long long ctr[3] = {0, 0, 0};
+    std::vector<int64_t> toff;
+    std::vector<unsigned long long> last_eq;    // per region: its last kept count, entries with it
+    int64_t cap2 = 0;                           // places per region in kept
+    std::vector<int32_t> nk((size_t)na, 0);
+    std::vector<A2CVarEntry> kept;
+    const unsigned wave_blocks = (unsigned)std::min<int64_t>((np + 3) / 4, 8192);
+    hipError_t e = hipMalloc(&d_win, sizeof(int64_t) * win.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), sizeof(int64_t) * win.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMalloc(&d_h, sizeof(uint64_t) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_ctr, sizeof(ctr));
+    if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, sizeof(ctr), s);
+    if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants alloc"); goto done; }
+    a.text = S.d_text;
+    a.rows = S.d_rows + S.g_first[g];
+    a.win = d_win;
+    a.n_rows = nr;
+    a.n_pairs = np;
+    a.key_bits = key_bits;
+    a.h = d_h;
+    a.ctr = d_ctr;
+    {
+        const int p0 = prof_begin(c, "k_a2c_var_hash");
+        hipLaunchKernelGGL(k_a2c_var_hash, dim3(wave_blocks), dim3(256), 0, s, a);
+        prof_end(c, p0);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_hash"); goto done; }
+    S.var_stats[0] = (int64_t)ctr[0];
+    if (ctr[0] == 0) goto done;
+    while (tsize < 2 * ctr[0]) tsize <<= 1;
+    e = hipMalloc(&d_tkey, sizeof(uint64_t) * tsize);
+    if (e == hipSuccess) e = hipMalloc(&d_tcnt, sizeof(unsigned long long) * tsize);
+    if (e == hipSuccess) e = hipMalloc(&d_tfirst, sizeof(uint32_t) * tsize);
+    if (e == hipSuccess) e = hipMalloc(&d_tregion, sizeof(int32_t) * tsize);
+    if (e == hipSuccess) e = hipMalloc(&d_ent, sizeof(A2CVarEntry) * ctr[0]);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tkey, 0, sizeof(uint64_t) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tcnt, 0, sizeof(unsigned long long) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tfirst, 0xff, sizeof(uint32_t) * tsize, s);
+    if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants table"); goto done; }
+    a.tkey = d_tkey;
+    a.tcnt = d_tcnt;
+    a.tfirst = d_tfirst;
+    a.tregion = d_tregion;
+    a.mask = tsize - 1;
+    a.entries = d_ent;
+    {
+        const int p0 = prof_begin(c, "k_a2c_var_count");
+        hipLaunchKernelGGL(k_a2c_var_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, a);
+        prof_end(c, p0);
+        const int p1 = prof_begin(c, "k_a2c_var_verify");
+        hipLaunchKernelGGL(k_a2c_var_verify, dim3(wave_blocks), dim3(256), 0, s, a);
+        prof_end(c, p1);
+        const int p2 = prof_begin(c, "k_a2c_var_compact");
+        hipLaunchKernelGGL(k_a2c_var_compact, dim3((unsigned)((tsize + 255) / 256)), dim3(256), 0, s, a);
+        prof_end(c, p2);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_count"); goto done; }
+    if (ctr[1]) {
+        set_error("aln2counts: variant hash collision (distinct clipped sequences share a key)");
+        rc = -4;
+        goto done;
+    }
+    S.var_stats[1] = (int64_t)ctr[2];
+    // ---- the cut: every slice's greatest entries, then each region's among those ----
+    {
+        const int64_t n_ent = (int64_t)ctr[2];
+        int64_t most = 0;
+        for (int k = 0; k < na; ++k) most = std::max(most, win[4 * (size_t)k + 3]);
+        const int64_t n_slices = (n_ent + A2C_VAR_SLICE - 1) / A2C_VAR_SLICE;
+        const int64_t cap1 = std::min<int64_t>(most, A2C_VAR_SLICE), seg = n_slices * cap1;
+        const int64_t n_cand = n_slices > 1 ? (int64_t)na * seg : 0;
+        cap2 = std::min<int64_t>(most, n_slices > 1 ? seg : n_ent);
+        const size_t slots = (size_t)na * (size_t)std::max<int64_t>(n_slices, 1);
+        e = hipMalloc(&d_state, (size_t)(n_ent + n_cand));
+        if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, (size_t)(n_ent + n_cand), s);
+        if (e == hipSuccess) e = hipMalloc(&d_kept, sizeof(A2CVarEntry) * (size_t)na * (size_t)cap2);
+        if (e == hipSuccess) e = hipMalloc(&d_nkept, sizeof(int32_t) * 2 * slots);
+        if (e == hipSuccess) e = hipMalloc(&d_last, sizeof(unsigned long long) * (2 * slots + (size_t)na));
+        if (e == hipSuccess) e = hipMemsetAsync(d_last, 0, sizeof(unsigned long long) * (2 * slots + (size_t)na), s);
+        if (e == hipSuccess && n_cand) e = hipMalloc(&d_cand, sizeof(A2CVarEntry) * (size_t)n_cand);
+        if (e == hipSuccess && n_cand) e = hipMemsetAsync(d_cand, 0xff, sizeof(A2CVarEntry) * (size_t)n_cand, s);
+        if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants select"); goto done; }
+        // d_nkept / d_last: [0, slots) the regions' results, [slots, 2 slots) the slices'
+        const int p0 = prof_begin(c, "k_a2c_var_select");
+        if (n_slices > 1) {
+            hipLaunchKernelGGL(k_a2c_var_select, dim3((unsigned)n_slices, (unsigned)na), dim3(1024), 0, s, a,
+                               d_ent, n_ent, (int64_t)A2C_VAR_SLICE, (int64_t)0, d_state, cap1, d_cand,
+                               d_nkept + slots, d_last + slots);
+            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, d_cand, n_cand,
+                               seg, seg, d_state + n_ent, cap2, d_kept, d_nkept, d_last);
+        } else {
+            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, d_ent, n_ent,
+                               n_ent, (int64_t)0, d_state, cap2, d_kept, d_nkept, d_last);
+        }
+        prof_end(c, p0);
+        const int p1 = prof_begin(c, "k_a2c_var_tied");
+        hipLaunchKernelGGL(k_a2c_var_tied, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, a, n_ent,
+                           d_last, d_last + 2 * slots);
+        prof_end(c, p1);
+        e = hipGetLastError();
+        kept.resize((size_t)na * (size_t)cap2);
+        last_eq.resize(2 * (size_t)na);
+        if (e == hipSuccess) e = hipMemcpyAsync(nk.data(), d_nkept, sizeof(int32_t) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && !kept.empty())
+            e = hipMemcpyAsync(kept.data(), d_kept, sizeof(A2CVarEntry) * kept.size(), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data(), d_last, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data() + na, d_last + 2 * slots, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_select"); goto done; }
+    }
+    // ---- the kept entries' text: their summed lengths and nothing else ----
+    {
+        std::vector<A2CVarEntry> order;
+        for (int k = 0; k < na; ++k) {
+            if (nk[(size_t)k] < 0 || nk[(size_t)k] > cap2) {
+                set_error("mh_a2c_variants: the selection is inconsistent");
+                rc = -3;
+                goto done;
+            }
+            int64_t at_last = 0;
+            for (int32_t i = 0; i < nk[(size_t)k]; ++i) {
+                order.push_back(kept[(size_t)k * (size_t)cap2 + i]);
+                S.var_region.push_back(which[(size_t)k]);
+                at_last += order.back().count == last_eq[(size_t)k];
+            }
+            // a cut inside a tie: entries left out that share the last kept count
+            if (nk[(size_t)k] == win[4 * (size_t)k + 3] && (int64_t)last_eq[(size_t)na + k] > at_last)
+                S.var_stats[2] += (int64_t)last_eq[(size_t)na + k];
+            if (n_kept) n_kept[which[(size_t)k]] = nk[(size_t)k];
+        }
+        toff.assign(order.size() + 1, 0);
+        for (size_t k = 0; k < order.size(); ++k) toff[k + 1] = toff[k] + order[k].len;
+        S.var_text.assign((size_t)toff.back(), '\0');
+        if (toff.back() > 0) {
+            e = hipMalloc(&d_toff, sizeof(int64_t) * toff.size());
+            if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)toff.back());
+            if (e == hipSuccess) e = hipMemcpyAsync(d_toff, toff.data(), sizeof(int64_t) * toff.size(), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_kept, order.data(), sizeof(A2CVarEntry) * order.size(), hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants gather"); goto done; }
+            const int p0 = prof_begin(c, "k_a2c_var_gather");
+            hipLaunchKernelGGL(k_a2c_var_gather, dim3((unsigned)((order.size() + 3) / 4)), dim3(256), 0, s,
+                               a, d_kept, d_toff, (int64_t)order.size(), d_out);
+            prof_end(c, p0);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&S.var_text[0], d_out, (size_t)toff.back(), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_gather"); goto done; }
+            S.var_stats[3] = toff.back();
+        }
+        S.var_entries = std::move(order);
+    }
+done:
+    hipFree(d_win); hipFree(d_last); hipFree(d_cand); hipFree(d_toff); hipFree(d_h); hipFree(d_tkey); hipFree(d_tcnt);
+    hipFree(d_ctr); hipFree(d_tfirst); hipFree(d_tregion); hipFree(d_nkept); hipFree(d_ent);
+    hipFree(d_kept); hipFree(d_state); hipFree(d_out);
+    prof_flush(c);
+    S.t_var = ms_since(t0);
+    if (rc) {
+        S.var_entries.clear();
+        S.var_region.clear();
+        S.var_text.clear();
+        if (n_kept) for (int k = 0; k < n_regions; ++k) n_kept[k] = 0;
+    }
+    return rc;
+}
+
+extern "C" int mh_a2c_variant_entries(mh_ctx *ctx, int slot, int32_t *region, int64_t *count,
+                                      int32_t *len, char *seqs, size_t cap, size_t *used)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    for (size_t k = 0; k < S.var_entries.size(); ++k) {
+        if (region) region[k] = S.var_region[k];
+        if (count) count[k] = (int64_t)S.var_entries[k].count;
+        if (len) len[k] = S.var_entries[k].len;
+    }
+    if (used) *used = S.var_text.size();
+    if (seqs) {
+        if (cap < S.var_text.size()) { set_error("mh_a2c_variant_entries: buffer too small"); return -2; }
+        memcpy(seqs, S.var_text.data(), S.var_text.size());
+    }
+    return 0;
+}
+
+extern "C" int mh_a2c_variant_stats(mh_ctx *ctx, int slot, int64_t *stats4, double *ms)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || !stats4) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    for (int k = 0; k < 4; ++k) stats4[k] = S.var_stats[k];
+    if (ms) *ms = S.t_var;
     return 0;
 }

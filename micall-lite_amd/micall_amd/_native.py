@@ -199,6 +199,11 @@ def _declare(L):
         'mh_a2c_insert_entries': ([_P, ctypes.c_int, _P, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_a2c_timing': ([_P, ctypes.c_int, _P], ctypes.c_int),
+        'mh_a2c_variants': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P, ctypes.c_int,
+                             _P], ctypes.c_int),
+        'mh_a2c_variant_entries': ([_P, ctypes.c_int, _P, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_a2c_variant_stats': ([_P, ctypes.c_int, _P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         'mh_fastq_open_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 ctypes.POINTER(_P), _I64P], ctypes.c_int),
         'mh_fastq_scan_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I64P],
@@ -859,6 +864,39 @@ class Context:
                                           ctypes.byref(used)), 'mh_a2c_insert_entries')
         aminos = buf.raw[:used.value].decode().split('\n')[:k]
         return [(int(rng[i]), int(cnt[i]), int(first[i]), aminos[i]) for i in range(k)]
+
+    VARIANT_STATS = ('pairs', 'entries', 'tied_at_cut', 'text_bytes')
+
+    def a2c_variants(self, slot, g, starts, ends, ref_lens, max_variants, key_bits=64):
+        """mh_a2c_variants over group g, then the kept entries:
+        ([(region index, count, clipped sequence bytes)] in report order,
+        stats dict of VARIANT_STATS plus 'ms').  A hash collision (only with a
+        small key_bits) raises NativeError and returns nothing."""
+        n = len(starts)
+        arr = [np.array(list(v) or [0], dtype=np.int64) for v in (starts, ends, ref_lens, max_variants)]
+        kept = np.zeros(max(n, 1), dtype=np.int64)
+        check(lib().mh_a2c_variants(self.h, slot, g, n, _ptr(arr[0]), _ptr(arr[1]), _ptr(arr[2]),
+                                    _ptr(arr[3]), int(key_bits), _ptr(kept)), 'mh_a2c_variants')
+        k = int(kept[:n].sum())
+        rg = np.zeros(max(k, 1), np.int32)
+        cnt = np.zeros(max(k, 1), np.int64)
+        ln = np.zeros(max(k, 1), np.int32)
+        used = ctypes.c_size_t()
+        check(lib().mh_a2c_variant_entries(self.h, slot, _ptr(rg), _ptr(cnt), _ptr(ln), None, 0,
+                                           ctypes.byref(used)), 'mh_a2c_variant_entries')
+        buf = ctypes.create_string_buffer(max(used.value, 1))
+        check(lib().mh_a2c_variant_entries(self.h, slot, None, None, None, buf, len(buf),
+                                           ctypes.byref(used)), 'mh_a2c_variant_entries')
+        text, at, out = buf.raw[:used.value], 0, []
+        for i in range(k):
+            out.append((int(rg[i]), int(cnt[i]), text[at:at + int(ln[i])]))
+            at += int(ln[i])
+        st = np.zeros(4, dtype=np.int64)
+        ms = ctypes.c_double()
+        check(lib().mh_a2c_variant_stats(self.h, slot, _ptr(st), ctypes.byref(ms)), 'mh_a2c_variant_stats')
+        stats = dict(zip(self.VARIANT_STATS, (int(x) for x in st)))
+        stats['ms'] = ms.value
+        return out, stats
 
     def a2c_timing(self, slot):
         out = np.zeros(3, dtype=np.float64)

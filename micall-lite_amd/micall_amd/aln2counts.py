@@ -27,7 +27,11 @@ unchanged.  Differences that never reach an output file:
   * the progress callback hears the start and the end of each run, not every
     1 % of the file (aln2counts.py:136-141);
   * the nucleotide variant counts that the reference computes and drops
-    (aln2counts.py:346-375) are not computed;
+    (aln2counts.py:346-375) are computed only when asked for
+    (SequenceReport.count_variants / write_variants, aln2counts(variants_csv=),
+    --variants_csv): the report write_nuc_variants was meant to write, counted
+    on the device (mh_a2c_variants).  write_nuc_variants / nuc_variants_csv
+    fail as the reference's do;
   * an InsertionWriter fed by a SequenceReport reads the run's rows from the
     device, so its nuc_seqs stays empty;
   * characters other than A C G T N - n, negative offsets and counts of 2**32
@@ -291,6 +295,18 @@ class _LazySeedAmino(object):
         return repr(self._frame.seed_amino(self.consensus_index))
 
 
+def _variant_window(conseq_index):
+    """[start, end) in padded read positions of a coordinate region's
+    variants, from the consensus codon of every coordinate position (-1:
+    none): three times the first one to three times the last one plus one.
+    A last codon of 0 counts as none (the reference's `or -1`,
+    aln2counts.py:360), which empties the window."""
+    placed = [int(k) for k in conseq_index if k >= 0]
+    first = placed[0] if placed else 0
+    last = (placed[-1] if placed else 0) or -1
+    return 3 * first, 3 * (last + 1)
+
+
 class _CoordinateMap(object):
     """Where one coordinate region sits in a run: the chosen reading frame,
     and per coordinate position the consensus codon index (-1: none)."""
@@ -364,6 +380,9 @@ class SequenceReport(object):
             setattr(self, name, {})
         self._frames = None
         self._coord_maps = {}
+        self._run = run
+        self._variants_counted = False
+        self.variant_stats = None
         if run is not None:
             self.seed, self.qcut = run.seed, run.qcut
             self.insert_writer.start_group(run.seed, run.qcut)
@@ -547,6 +566,36 @@ class SequenceReport(object):
         """The reference sorts dict.keys() in place here, which fails under
         Python 3 with AttributeError; so does this (no output either way)."""
         getattr(self.variants.keys(), 'sort')()
+
+    def count_variants(self):
+        """{coordinate region: [(count, clipped sequence), ...]} of the run
+        just read: for every region a reading frame aligned to, the reads
+        clipped to the region's consensus codons (aln2counts.py:346-375),
+        equal ones added up, the projects' max_variants greatest by (count,
+        sequence).  One device call for all regions, made once per read and
+        only when asked (mh_a2c_variants; its figures in variant_stats)."""
+        if self._variants_counted:
+            return self.variants
+        names = sorted(name for name, report in self.reports.items() if report)
+        self.variants = {name: [] for name in names}
+        if names and self._run is not None:
+            windows = [_variant_window(self._coord_maps[name].conseq_index) for name in names]
+            found, self.variant_stats = self._run.ctx.a2c_variants(
+                self._run.slot, self._run.group, [w[0] for w in windows], [w[1] for w in windows],
+                [len(self.coordinate_refs[name]) for name in names],
+                [self.projects.getMaxVariants(name) for name in names])
+            for k, count, seq in found:
+                self.variants[names[k]].append((count, seq.decode('ascii')))
+        self._variants_counted = True
+        return self.variants
+
+    def write_variants(self, variants_file):
+        """The rows write_nuc_variants (aln2counts.py:537-549) was meant to
+        write: regions in name order, each one's variants from index 0."""
+        variants = self.count_variants()
+        out = _csv_writer(variants_file, 'nuc_variants')
+        out.writerows(dict(seed=self.seed, qcut=self.qcut, region=name, index=i, count=count, seq=seq)
+                      for name in sorted(variants) for i, (count, seq) in enumerate(variants[name]))
 
     def write_failure(self, fail_file):
         """One row per coordinate region that no reading frame aligned to."""
@@ -744,10 +793,13 @@ _SHARD = None      # the job's Shard while a sharded aln2counts runs (InsertionW
 
 def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
-               coverage_summary_csv=None, json=None):
+               coverage_summary_csv=None, json=None, variants_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
+    variants_csv takes the top nucleotide variants of every coordinate region
+    (SequenceReport.write_variants); nuc_variants_csv fails as the
+    reference's does.
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -755,19 +807,28 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     job's counters, and rank 0 writes them (session.writer_stage).  The
     insertion strings are counted the same way (InsertionWriter.write).
     When aligned.csv cannot be split (not a plain file on every rank, '\r'
-    or quoted fields), rank 0 computes alone while the others wait."""
+    or quoted fields), rank 0 computes alone while the others wait; so it
+    does when any rank was given variants_csv (the variants are counted over
+    all rows of a run at once, not merged across ranks)."""
     global _SHARD
     sh = session.shard()
     SHARD_STATS.clear()
     session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
-               coverage_summary_csv)
+               coverage_summary_csv, variants_csv)
     with session.writer_stage(*handles) as stage:
-        groups = _load_sharded(sh, aligned_csv) if sh is not None else None
+        split = sh is not None
+        if split:
+            from .sharded_io import _agree_ok
+            if not _agree_ok(sh, variants_csv is None):    # asked for on some rank
+                split = False
+                SHARD_STATS.update(mode='unsplit', reason='variants_csv')
+        groups = _load_sharded(sh, aligned_csv) if split else None
         if groups is None:
             if stage.active:
                 _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
-                            failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json)
+                            failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
+                            variants_csv=variants_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -835,7 +896,8 @@ def _load_sharded(sh, aligned_csv):
 
 
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
-                nuc_variants_csv, callback, coverage_summary_csv, json, groups=None):
+                nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
+                variants_csv=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -852,6 +914,9 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if nuc_variants_csv:
         report.write_nuc_variants_header(nuc_variants_csv)
         per_run.append(lambda: report.write_nuc_variants(nuc_variants_csv))
+    if variants_csv is not None:
+        report.write_nuc_variants_header(variants_csv)
+        per_run.append(lambda: report.write_variants(variants_csv))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -898,6 +963,8 @@ def _arguments():
                      help='output: consensus sequences that did not align')
     cli.add_argument('--nuc_variants_csv', type=argparse.FileType('w'),
                      help='output: nucleotide variants')
+    cli.add_argument('--variants_csv', type=argparse.FileType('w'),
+                     help='output: top nucleotide variants of every coordinate region')
     return cli.parse_args()
 
 
@@ -907,7 +974,7 @@ parseArgs = _arguments
 def main():
     a = _arguments()
     aln2counts(a.aligned_csv, a.nuc_csv, a.amino_csv, a.coord_ins_csv, a.conseq_csv,
-               a.failed_align_csv, a.nuc_variants_csv)
+               a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv)
 
 
 if __name__ == '__main__':

@@ -14,27 +14,35 @@ import os
 
 DEFAULT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data',
                             'micall_regions.json')
+MAX_VARIANTS_PATH = os.path.join(os.path.dirname(DEFAULT_PATH), 'project_max_variants.json')
 
 
 class ProjectConfig(object):
     def __init__(self, regions=None, project_seed_regions=None, json_file=None,
-                 project_regions=None):
+                 project_regions=None, max_variants=None):
         self.regions = regions or {}                # {name: {'seq', 'seed_group'}}
         self.project_seed_regions = project_seed_regions or {}  # {project: [seed names]}
         # {project: [[coordinate region, [seed names]], ...]} in file order
         self.project_regions = project_regions or {}
+        self.max_variants = max_variants or {}      # {project: variants to report}; 0 when absent
         self.json_file = json_file
 
     @classmethod
     def from_config(cls, cfg, json_file=None):
         """From a parsed projects file: the reference's projects.json format
-        or this package's data/micall_regions.json."""
+        or this package's data/micall_regions.json (whose projects'
+        max_variants are its own 'max_variants' table when it has one, else
+        data/project_max_variants.json)."""
         if 'project_seed_regions' in cfg:
+            limits = cfg.get('max_variants')
+            if limits is None:
+                with open(MAX_VARIANTS_PATH) as f:
+                    limits = json.load(f)
             return cls(cfg['regions'], cfg['project_seed_regions'], json_file,
-                       cfg.get('project_regions'))
+                       cfg.get('project_regions'), limits)
         regions = {name: {'seq': ''.join(r['reference']), 'seed_group': r.get('seed_group')}
                    for name, r in cfg['regions'].items()}
-        projects, links = {}, {}
+        projects, links, limits = {}, {}, {}
         for pname, p in cfg['projects'].items():
             seeds = set()
             for r in p['regions']:
@@ -42,7 +50,8 @@ class ProjectConfig(object):
             projects[pname] = sorted(seeds)
             links[pname] = [[r['coordinate_region'], list(r['seed_region_names'])]
                             for r in p['regions']]
-        return cls(regions, projects, json_file, links)
+            limits[pname] = int(p.get('max_variants', 0))
+        return cls(regions, projects, json_file, links, limits)
 
     def load(self, json_file):
         """project_config.ProjectConfig.load (:39-41) from an open file."""
@@ -98,6 +107,16 @@ class ProjectConfig(object):
                 if seed_region in seed_names and coord_region:
                     coord_refs[coord_region] = self.getReference(coord_region)
         return coord_refs
+
+    def getMaxVariants(self, coordinate_region):
+        """The largest max_variants of any project that lists the coordinate
+        region, 0 if none does (project_config.py:87-100)."""
+        most = 0
+        for pname, links in self.project_regions.items():
+            for coord_region, _ in links:
+                if coord_region == coordinate_region:
+                    most = max(self.max_variants.get(pname, 0), most)
+        return most
 
     def getSeedGroup(self, seed_region):
         return self.regions[seed_region]['seed_group']
