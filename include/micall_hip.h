@@ -587,8 +587,32 @@ int mh_censor_staged_write(mh_ctx *ctx, mh_fastq *fq, int n_bad, const char *con
                            const int32_t *cycles, int dst_gzip, int fd, int64_t offset,
                            int64_t *written, int64_t *base_count, int64_t *score_sum);
 /* Host wall ms of the last call: [0] gunzip + record split, [1] upload +
- * k_censor + download, [2] rewrite + gzip. */
+ * k_censor (+ k_trim) + download, [2] rewrite + gzip. */
 int mh_censor_timing(mh_ctx *ctx, double *ms3);
+/* 3' adapter trimming inside the censor pass (micall_amd.trim_fastqs; the
+ * step bin/micall:133 names and does not have).  The adapters hold for this
+ * context's following mh_censor_fastq / mh_censor_staged /
+ * mh_censor_staged_write calls; n1 = n2 = 0 clears them.  seqs1 (n1 of them)
+ * apply to the records whose header says read 1, seqs2 to all others: 0 to
+ * 8 adapters each, 3 to 64 bases of ACGT.  max_errors[i], i = 0..64, is the
+ * number of errors allowed in a match of i adapter bases (0 <= max_errors[i]
+ * < max(i, 1)); min_overlap >= 1 is the shortest adapter prefix accepted at
+ * the read's end.  Anything else: -3 and a message.
+ * After k_censor, k_trim compares each record's censored sequence line (its
+ * kept length n; an 'N' matches nothing) with each adapter a of its
+ * direction: c(i, j) = the smallest unit-cost edit distance between a[:i]
+ * and any r[s:j], s(i, j) the smallest such s.  Candidates are (m, j) for
+ * every j with c <= max_errors[m] and (i, n) for min_overlap <= i < m with
+ * c <= max_errors[i]; the smallest s wins (then the smaller c, the larger i,
+ * the lower adapter index) and the sequence and quality lines are cut to s.
+ * base_count / score_sum keep their meaning.  A record that keeps more than
+ * 65 535 bases fails the call (-3, the record named). */
+int mh_censor_set_adapters(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                           const char *const *seqs2, int min_overlap, const int32_t *max_errors);
+/* What the last censor call trimmed: reads[d * 8 + k] records won by adapter
+ * k of direction d (0: read 1, 1: the others), bases[...] the bases they
+ * lost.  16 entries each; zero after mh_censor_set_adapters. */
+int mh_censor_trim_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases);
 
 /* ---- aln2counts: replaces the per-read loops of aln2counts.py ---------- */
 /* aligned.csv text (refname, qcut, count, offset, seq columns) read as

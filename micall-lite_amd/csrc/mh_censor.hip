@@ -13,6 +13,12 @@
 //             dropped (the reference only flushes pending Ns before a good
 //             cycle, :66-74, :78-90), and every quality score is summed for
 //             the summary (:80-82) -- per-block sums, one atomic per block
+//   k_trim    only with adapters set (mh_censor_set_adapters; no such step
+//             in the reference, bin/micall:133 names it): one wave64 per
+//             read, the censored sequence line against each 3' adapter of
+//             its read direction by a semi-global unit-cost edit distance
+//             (lane l = adapter row l + 1, skewed along the read); the
+//             kept lengths are lowered to the leftmost match's start
 //   host      records rewritten (header and '+' lines verbatim) and, for
 //             gzip output, compressed, in blocks of ~8 MB of records on
 //             every host thread (one gzip member per block: the member
@@ -42,6 +48,20 @@
 
 namespace mh {
 
+constexpr int TRIM_MAXADAPT = 8;     // adapters per read direction
+constexpr int TRIM_MAXLEN = 64;      // adapter bases: one lane per adapter row
+constexpr int TRIM_MAXREAD = 65535;  // read bases: a match's start is 16 bits of a DP cell
+
+// the adapters as k_trim reads them: slot = direction * TRIM_MAXADAPT + index,
+// direction 0 for the records of read 1 (sign +1), 1 for all others
+struct TrimTab {
+    int32_t n[2];
+    int32_t min_overlap;
+    int32_t len[2 * TRIM_MAXADAPT];
+    int32_t max_err[TRIM_MAXLEN + 1];   // errors allowed in a match of i adapter bases
+    uint8_t seq[2 * TRIM_MAXADAPT][TRIM_MAXLEN];
+};
+
 struct CensorState {
     TextBuf text;                           // the FASTQ (censored in place)
     // per record: line starts (header, seq, '+', qual); the header line is
@@ -65,12 +85,21 @@ struct CensorState {
     uint32_t *d_bad = nullptr;
     unsigned long long *d_sums = nullptr;
     int64_t cap_text = 0, cap_rec = 0, cap_bad = 0;
+    // 3' adapters of the following calls (mh_censor_set_adapters) and what
+    // the last call trimmed, per direction * TRIM_MAXADAPT + adapter
+    bool trim_on = false;
+    TrimTab trim{};
+    int64_t trim_reads[2 * TRIM_MAXADAPT] = {}, trim_bases[2 * TRIM_MAXADAPT] = {};
+    TrimTab *d_trim = nullptr;
+    unsigned long long *d_tstat = nullptr;   // reads[16], bases[16]
 };
 
 static void censor_free_device(CensorState &C)
 {
     hipFree(C.d_text); hipFree(C.d_s0); hipFree(C.d_q0); hipFree(C.d_sl); hipFree(C.d_ql);
     hipFree(C.d_tile); hipFree(C.d_sign); hipFree(C.d_keep); hipFree(C.d_bad); hipFree(C.d_sums);
+    hipFree(C.d_trim); hipFree(C.d_tstat);
+    C.d_trim = nullptr; C.d_tstat = nullptr;
     C.d_text = nullptr; C.d_s0 = C.d_q0 = nullptr;
     C.d_sl = C.d_ql = C.d_tile = C.d_sign = C.d_keep = nullptr;
     C.d_bad = nullptr; C.d_sums = nullptr;
@@ -148,6 +177,124 @@ __global__ __launch_bounds__(256) void k_censor(CensorArgs A)
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += part_sum[w]; b += part_n[w]; }
         if (a) atomicAdd(&A.sums[0], (unsigned long long)a);
         if (b) atomicAdd(&A.sums[1], (unsigned long long)b);
+    }
+}
+
+// ---- k_trim: 3' adapters ---------------------------
+// For an adapter a (m bases) and the read r (n bases: the sequence line as
+// k_censor left it, cut to its kept length), cell (i, j) holds
+// K = cost << 16 | origin: the smallest unit-cost edit distance between
+// a[:i] and any r[s:j], and the smallest s that attains it,
+//   K[i][j] = min(K[i-1][j-1] + (a[i-1] != r[j-1]) << 16,
+//                 K[i-1][j] + 1 << 16, K[i][j-1] + 1 << 16),
+//   K[0][j] = j, K[i][0] = i << 16.
+// Candidates are (m, j) for every j with cost <= max_err[m], and (i, n) for
+// min_overlap <= i < m with cost <= max_err[i]; over the adapters of the
+// record's direction the smallest origin wins, then the smaller cost, the
+// larger i, the lower adapter index, which is the order of the 31-bit key
+//   origin << 15 | cost << 9 | (64 - i) << 3 | adapter
+// (a candidate's cost is below 64: max_err[i] < i <= 64).
+//
+// One wave per read.  Lane l owns row l + 1 and at step t stands in column
+// t - l + 1, so "up" is the lane below's cell of the step before (one lane
+// shift) and "diagonal" the value shifted in the step before that; lane 0
+// takes row 0's K[0][t + 1] = t + 1.  The read's bytes walk up the lanes by
+// the same shift: 64 of them are loaded at a time, one block ahead, and lane
+// 0 takes byte t of the block in hand each step.
+struct TrimArgs {
+    const uint8_t *text;
+    const int64_t *s0;
+    const int32_t *sign;
+    int64_t n;
+    int32_t *keep;
+    const TrimTab *tab;
+    unsigned long long *stat;   // [slot] reads, [16 + slot] bases
+};
+
+// lane l <- lane l - 1 (lane 0 takes `first`)
+__device__ __forceinline__ uint32_t trim_shift_up(uint32_t first, uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138, 0xF, 0xF, false);
+}
+
+__global__ __launch_bounds__(256) void k_trim(TrimArgs A)
+{
+    constexpr int NS = 2 * TRIM_MAXADAPT;
+    __shared__ unsigned long long part[4][2 * NS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const TrimTab &T = *A.tab;
+    const int min_ov = __builtin_amdgcn_readfirstlane(T.min_overlap);
+    unsigned long long my_reads = 0, my_bases = 0;   // lane k < NS: of slot k
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < A.n; r += (int64_t)gridDim.x * 4) {
+        const int dir = __builtin_amdgcn_readfirstlane(A.sign[r] == 1 ? 0 : 1);
+        const int n = __builtin_amdgcn_readfirstlane(A.keep[2 * r]);
+        const int na = __builtin_amdgcn_readfirstlane(T.n[dir]);
+        // a longer read is left alone: the host fails the call for it
+        if (n <= 0 || n > TRIM_MAXREAD || na <= 0) continue;
+        const uint8_t *rd = A.text + A.s0[r];
+        auto block = [&](int p) { return p + lane < n ? (uint32_t)rd[p + lane] : 0u; };
+        uint32_t best = ~0u;
+        for (int k = 0; k < na; ++k) {
+            const int slot = dir * TRIM_MAXADAPT + k;
+            const int m = __builtin_amdgcn_readfirstlane(T.len[slot]);
+            const bool row = lane < m;
+            const uint32_t ab = T.seq[slot][lane];
+            // a cell is within the row's error budget when it is <= vmax
+            const uint32_t vmax = (uint32_t)T.max_err[lane + 1] << 16 | 0xffffu;
+            const uint32_t ktail = (uint32_t)(63 - lane) << 3 | (uint32_t)k;
+            // of a cell with its halves swapped (origin above cost)
+            auto key = [&](uint32_t w) { return (w >> 16) << 15 | (w & 0xffffu) << 9 | ktail; };
+            const bool last = lane == m - 1;
+            uint32_t cur = (uint32_t)(lane + 1) << 16, diag = (uint32_t)lane << 16;
+            uint32_t rb = 0, full = ~0u;   // full: the least swapped cell of row m within budget
+            uint32_t nxt = block(0);
+            const int steps = n + m - 1;
+            for (int t0 = 0; t0 < steps; t0 += 64) {
+                const uint32_t blk = nxt;
+                nxt = block(t0 + 64);
+                auto step = [&](int q) {
+                    const int t = t0 + q;
+                    rb = trim_shift_up((uint32_t)__builtin_amdgcn_readlane((int)blk, q), rb);
+                    const uint32_t up = trim_shift_up((uint32_t)(t + 1), cur);
+                    const uint32_t v = min(diag + (ab != rb ? 0x10000u : 0u), min(up, cur) + 0x10000u);
+                    diag = up;
+                    // column j = t - lane + 1 is in 1 .. n (selects, no branch)
+                    const bool act = row && (uint32_t)(t - lane) < (uint32_t)n;
+                    cur = act ? v : cur;
+                    const uint32_t swapped = v >> 16 | v << 16;
+                    full = min(full, act && last && v <= vmax ? swapped : ~0u);
+                };
+                // four steps a turn (the shifts keep the compiler from
+                // unrolling): a step past the last one finds no row active
+                const int qn = min(64, (steps - t0 + 3) & ~3);
+                for (int q = 0; q < qn; q += 4) {
+                    step(q);
+                    step(q + 1);
+                    step(q + 2);
+                    step(q + 3);
+                }
+            }
+            // lane m - 1 holds the best full match, a lane below it its
+            // prefix's cell at the read's end
+            if (last) best = min(best, full == ~0u ? ~0u : key(full));
+            else if (row && lane + 1 >= min_ov && cur <= vmax) best = min(best, key(cur >> 16 | cur << 16));
+        }
+        for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
+        if (best == ~0u) continue;
+        const int s = (int)(best >> 15);
+        const int slot = dir * TRIM_MAXADAPT + (int)(best & 7u);
+        if (lane == 0) {
+            A.keep[2 * r] = s;
+            A.keep[2 * r + 1] = min(A.keep[2 * r + 1], s);
+        }
+        if (lane == slot) { ++my_reads; my_bases += (unsigned long long)(n - s); }
+    }
+    if (lane < NS) { part[wv][lane] = my_reads; part[wv][NS + lane] = my_bases; }
+    __syncthreads();
+    if (threadIdx.x < 2 * NS) {
+        unsigned long long a = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) a += part[w][threadIdx.x];
+        if (a) atomicAdd(&A.stat[threadIdx.x], a);
     }
 }
 
@@ -259,6 +406,8 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     const int64_t nr = (int64_t)C.h0.size();
     C.keep.assign(2 * (size_t)nr, 0);
     C.base_count = C.score_sum = 0;
+    std::fill(std::begin(C.trim_reads), std::end(C.trim_reads), 0);
+    std::fill(std::begin(C.trim_bases), std::end(C.trim_bases), 0);
     if (nr == 0) return 0;
     // bad-cycle bitmaps per bad tile id, over the cycles of the reads
     int maxc = 1;
@@ -302,6 +451,9 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
         H(hipMalloc(&D.d_bad, 4 * bm.size()), "hipMalloc");
     }
     if (!D.d_sums) H(hipMalloc(&D.d_sums, 16), "hipMalloc");
+    constexpr size_t tstat_bytes = 2 * 2 * TRIM_MAXADAPT * sizeof(unsigned long long);
+    if (C.trim_on && !D.d_trim) H(hipMalloc(&D.d_trim, sizeof(TrimTab)), "hipMalloc");
+    if (C.trim_on && !D.d_tstat) H(hipMalloc(&D.d_tstat, tstat_bytes), "hipMalloc");
     if (st) { censor_free_device(D); return st; }
     H(hipMemcpyAsync(D.d_text, C.text.data(), C.text.size(), hipMemcpyHostToDevice, s), "H2D");
     H(hipMemcpyAsync(D.d_s0, C.s0.data(), 8 * nr, hipMemcpyHostToDevice, s), "H2D");
@@ -322,6 +474,19 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
         prof_end(c, pk);
         H(hipGetLastError(), "k_censor");
     }
+    unsigned long long tstat[2 * 2 * TRIM_MAXADAPT] = {};
+    if (C.trim_on && !st) {   // on the censored text, before it goes down
+        H(hipMemcpyAsync(D.d_trim, &C.trim, sizeof(TrimTab), hipMemcpyHostToDevice, s), "H2D");
+        H(hipMemsetAsync(D.d_tstat, 0, tstat_bytes, s), "memset");
+        TrimArgs ta{D.d_text, D.d_s0, D.d_sign, nr, D.d_keep, D.d_trim, D.d_tstat};
+        if (!st) {
+            const int pk = prof_begin(c, "k_trim");
+            hipLaunchKernelGGL(k_trim, dim3((unsigned)blocks), dim3(256), 0, s, ta);
+            prof_end(c, pk);
+            H(hipGetLastError(), "k_trim");
+        }
+        H(hipMemcpyAsync(tstat, D.d_tstat, tstat_bytes, hipMemcpyDeviceToHost, s), "D2H");
+    }
     unsigned long long sums[2] = {0, 0};
     H(hipMemcpyAsync(C.text.data(), D.d_text, C.text.size(), hipMemcpyDeviceToHost, s), "D2H");
     H(hipMemcpyAsync(C.keep.data(), D.d_keep, 8 * nr, hipMemcpyDeviceToHost, s), "D2H");
@@ -331,6 +496,25 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     prof_flush(c);
     C.score_sum = (long long)sums[0];
     C.base_count = (long long)sums[1];
+    if (C.trim_on) {
+        // k_trim leaves a read past its cap alone (its kept length is still
+        // k_censor's): such a read fails the call
+        if (maxc > TRIM_MAXREAD)
+            for (int64_t r = 0; r < nr; ++r)
+                if (C.keep[2 * r] > TRIM_MAXREAD) {
+                    const char *h = C.text.data() + C.h0[r];
+                    const int hl = (int)std::min<int64_t>(C.s0[r] - C.h0[r], 80);
+                    int e = 0;
+                    while (e < hl && !py_space((unsigned char)h[e])) ++e;
+                    set_error("censor: record %lld (%.*s) keeps %d bases, adapter trimming takes reads "
+                              "of at most %d", (long long)(r + 1), e, h, (int)C.keep[2 * r], TRIM_MAXREAD);
+                    return -3;
+                }
+        for (int k = 0; k < 2 * TRIM_MAXADAPT; ++k) {
+            C.trim_reads[k] = (int64_t)tstat[k];
+            C.trim_bases[k] = (int64_t)tstat[2 * TRIM_MAXADAPT + k];
+        }
+    }
     return 0;
 }
 
@@ -597,5 +781,64 @@ extern "C" int mh_censor_timing(mh_ctx *ctx, double *ms3)
     ms3[0] = c.censor->t_host_in;
     ms3[1] = c.censor->t_device;
     ms3[2] = c.censor->t_host_out;
+    return 0;
+}
+
+extern "C" int mh_censor_set_adapters(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                                      const char *const *seqs2, int min_overlap,
+                                      const int32_t *max_errors)
+{
+    if (!ctx) return -3;
+    Ctx &c = *ctx_of(ctx);
+    if (!c.censor) c.censor = new CensorState();
+    CensorState &C = *c.censor;
+    std::fill(std::begin(C.trim_reads), std::end(C.trim_reads), 0);
+    std::fill(std::begin(C.trim_bases), std::end(C.trim_bases), 0);
+    if (n1 == 0 && n2 == 0) { C.trim_on = false; return 0; }
+    TrimTab T{};
+    const int n[2] = {n1, n2};
+    const char *const *seqs[2] = {seqs1, seqs2};
+    for (int d = 0; d < 2; ++d) {
+        if (n[d] < 0 || n[d] > TRIM_MAXADAPT || (n[d] && !seqs[d])) {
+            set_error("censor: %d adapters for read direction %d (0 to %d)", n[d], d + 1, TRIM_MAXADAPT);
+            return -3;
+        }
+        T.n[d] = n[d];
+        for (int k = 0; k < n[d]; ++k) {
+            const char *a = seqs[d][k];
+            const size_t m = a ? strnlen(a, TRIM_MAXLEN + 1) : 0;
+            if (m < 3 || m > (size_t)TRIM_MAXLEN || strspn(a, "ACGT") != m) {
+                set_error("censor: adapter %d of read direction %d is not 3 to %d bases of ACGT", k, d + 1,
+                          TRIM_MAXLEN);
+                return -3;
+            }
+            T.len[d * TRIM_MAXADAPT + k] = (int32_t)m;
+            memcpy(T.seq[d * TRIM_MAXADAPT + k], a, m);
+        }
+    }
+    if (min_overlap < 1) { set_error("censor: min_overlap %d is below 1", min_overlap); return -3; }
+    T.min_overlap = min_overlap;
+    if (!max_errors) { set_error("censor: no error table"); return -3; }
+    for (int i = 0; i <= TRIM_MAXLEN; ++i) {
+        // an error rate below 1 allows fewer than i errors in i bases
+        if (max_errors[i] < 0 || max_errors[i] >= std::max(i, 1)) {
+            set_error("censor: %d errors allowed in %d adapter bases", (int)max_errors[i], i);
+            return -3;
+        }
+        T.max_err[i] = max_errors[i];
+    }
+    C.trim = T;
+    C.trim_on = true;
+    return 0;
+}
+
+extern "C" int mh_censor_trim_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases)
+{
+    if (!ctx || !reads || !bases) return -3;
+    Ctx &c = *ctx_of(ctx);
+    for (int k = 0; k < 2 * TRIM_MAXADAPT; ++k) {
+        reads[k] = c.censor ? c.censor->trim_reads[k] : 0;
+        bases[k] = c.censor ? c.censor->trim_bases[k] : 0;
+    }
     return 0;
 }

@@ -182,6 +182,9 @@ def _declare(L):
                               ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_censor_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_censor_timing': ([_P, _P], ctypes.c_int),
+        'mh_censor_set_adapters': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, _P], ctypes.c_int),
+        'mh_censor_trim_stats': ([_P, _P, _P], ctypes.c_int),
         'mh_a2c_load_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
         'mh_a2c_insert_rows': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, _P, _P, ctypes.c_char_p,
                                 ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)],
@@ -666,6 +669,30 @@ class Context:
         out = np.zeros(3, dtype=np.float64)
         check(lib().mh_censor_timing(self.h, _ptr(out)), 'mh_censor_timing')
         return [float(x) for x in out]
+
+    def censor_set_adapters(self, adapters1, adapters2, min_overlap, max_errors):
+        """mh_censor_set_adapters: 3' adapters (str) of the records of read
+        1 / of all others for this context's following censor calls, with
+        max_errors[i], i = 0..64, errors allowed in i adapter bases; two
+        empty lists clear them."""
+        lists = []
+        for adapters in (adapters1, adapters2):
+            lists.append((ctypes.c_char_p * max(len(adapters), 1))(*[a.encode() for a in adapters]))
+        if len(max_errors) != 65:
+            raise ValueError('max_errors holds {} entries, not 65'.format(len(max_errors)))
+        table = np.array(max_errors, dtype=np.int32)
+        check(lib().mh_censor_set_adapters(self.h, len(adapters1), lists[0], len(adapters2), lists[1],
+                                           int(min_overlap), _ptr(table)), 'mh_censor_set_adapters')
+
+    def censor_clear_adapters(self):
+        check(lib().mh_censor_set_adapters(self.h, 0, None, 0, None, 0, None), 'mh_censor_set_adapters')
+
+    def censor_trim_stats(self):
+        """mh_censor_trim_stats of the last censor call: (reads, bases), each
+        [direction][adapter] with direction 0 = read 1."""
+        reads, bases = np.zeros(16, dtype=np.int64), np.zeros(16, dtype=np.int64)
+        check(lib().mh_censor_trim_stats(self.h, _ptr(reads), _ptr(bases)), 'mh_censor_trim_stats')
+        return reads.reshape(2, 8).tolist(), bases.reshape(2, 8).tolist()
 
     # ---- aln2counts -----------------------------------------------------
     def a2c_load_csv(self, slot, text, codon_chars):
