@@ -375,6 +375,24 @@ int mh_sam_parse(const char *text, int64_t len, mh_sam_sizes *sizes, int32_t *fl
                  int32_t *pos, int32_t *cigar_off, int32_t *n_cigar, uint32_t *cigar,
                  int64_t *seq_off, int32_t *seq_len, uint8_t *seq, uint8_t *qual, int64_t *units,
                  char *names, int32_t *ends);
+/* Host-only parse of prelim.csv text as mh_rows_load_csv parses it, no
+ * device: the sizes first (any array NULL), then the caller's arrays.  Per
+ * data row, in file order: the arrays mh_rows_load takes (ref is the compact
+ * reference id; CIGAR ops and QUAL as mh_sam_parse gives them), units, and
+ * what mh_rows_info gives: info[n_rows][4], present[n_present], unknown
+ * '\n'-joined (unknown_bytes + 1 bytes).  threads: host threads the text is
+ * cut over, 0 for the default; the result does not depend on it.  Returns -3
+ * (with a message) for an empty text, a missing column or a short row. */
+typedef struct {
+    int64_t n_rows, n_units, n_cigar, n_bases;
+    int32_t n_present;
+    size_t unknown_bytes;
+} mh_prelim_sizes;
+int mh_prelim_parse(const char *text, int64_t len, int n_refs, const char *const *refnames,
+                    int threads, mh_prelim_sizes *sizes, int32_t *flag, int32_t *ref, int32_t *pos,
+                    int32_t *cigar_off, int32_t *n_cigar, uint32_t *cigar, int64_t *seq_off,
+                    int32_t *seq_len, uint8_t *seq, uint8_t *qual, int64_t *units, int32_t *info,
+                    int32_t *present, char *unknown);
 /* dense: n_refs x cap x 4 int32 counts of A,C,G,T at positions 1..cap;
  * nflag/dflag: n_refs x cap bytes ('N' seen -> count -1, '-' seen -> -2);
  * read_counts: merged pairs per ref; first_unit: first merged unit index

@@ -618,22 +618,6 @@ static int a2c_tables(A2CState &S, const char *codon_chars)
     return 0;
 }
 
-// Python int() on a CSV field (surrounding whitespace, one sign)
-static bool a2c_int(const char *a, const char *b, int64_t &v)
-{
-    while (a < b && (*a == ' ' || *a == '\t' || *a == '\r' || *a == '\n' || *a == '\f' || *a == '\v')) ++a;
-    while (b > a && (b[-1] == ' ' || b[-1] == '\t' || b[-1] == '\r' || b[-1] == '\n' ||
-                     b[-1] == '\f' || b[-1] == '\v')) --b;
-    bool neg = false;
-    if (a < b && (*a == '+' || *a == '-')) { neg = *a == '-'; ++a; }
-    if (a == b) return false;
-    long long x = 0;
-    auto r = std::from_chars(a, b, x);
-    if (r.ec != std::errc() || r.ptr != b) return false;
-    v = neg ? -x : x;
-    return true;
-}
-
 struct A2CKey {
     const char *p;
     int32_t n;
@@ -655,11 +639,11 @@ static bool a2c_row(A2CPart &P, const char *const *fb, const char *const *fe, co
                     const char *base, const uint8_t *cls)
 {
     int64_t cnt = 0, off = 0;
-    if (!a2c_int(fb[col[COL_COUNT]], fe[col[COL_COUNT]], cnt)) {
+    if (!py_int(std::string_view(fb[col[COL_COUNT]], (size_t)(fe[col[COL_COUNT]] - fb[col[COL_COUNT]])), cnt)) {
         P.err = "invalid literal for int() with base 10 in column count";
         return false;
     }
-    if (!a2c_int(fb[col[COL_OFFSET]], fe[col[COL_OFFSET]], off)) {
+    if (!py_int(std::string_view(fb[col[COL_OFFSET]], (size_t)(fe[col[COL_OFFSET]] - fb[col[COL_OFFSET]])), off)) {
         P.err = "invalid literal for int() with base 10 in column offset";
         return false;
     }
@@ -717,25 +701,23 @@ static void a2c_parse_part(A2CPart &P, const int *col, int need, const char *bas
 static void a2c_parse_quoted(A2CPart &P, const int *col, int need, const uint8_t *cls,
                              std::string &seqpool)
 {
-    std::vector<std::string> f;
+    std::vector<std::string_view> f;
+    std::deque<std::string> scratch;
     std::vector<const char *> fb(need), fe(need);
     const char *p = P.beg;
     int64_t row = 0;
-    std::vector<size_t> seq_at;
-    while (p < P.end) {
-        csv_record(p, P.end, f);
+    while (csv_views(p, P.end, f, scratch)) {
         if (f.size() == 1 && f[0].empty()) continue;
         if ((int)f.size() < need) { P.err_row = row; P.err = "row has fewer fields than the header"; return; }
         for (int k = 0; k < need; ++k) {
-            P.pool.push_back(f[k]);
+            P.pool.emplace_back(f[k]);
             fb[k] = P.pool.back().data();
             fe[k] = fb[k] + P.pool.back().size();
         }
-        const std::string &sq = f[col[COL_SEQ]];
-        seq_at.push_back(seqpool.size());
-        seqpool.append(sq);
+        const size_t seq_at = seqpool.size();
+        seqpool.append(f[col[COL_SEQ]]);
         if (!a2c_row(P, fb.data(), fe.data(), col, fb[col[COL_SEQ]], cls)) { P.err_row = row; return; }
-        P.rows.back().soff = (int64_t)seq_at.back();
+        P.rows.back().soff = (int64_t)seq_at;
         ++row;
     }
 }
@@ -896,12 +878,8 @@ static int a2c_parse_csv(A2CState &S, const char *text, int64_t len, bool &use_p
     static const char *const want[N_COLS] = {"refname", "qcut", "count", "offset", "seq"};
     int col[N_COLS];
     int need = 0;
-    for (int k = 0; k < N_COLS; ++k) {
-        col[k] = -1;
-        for (size_t z = 0; z < head.size(); ++z)
-            if (head[z] == want[k]) col[k] = (int)z;     // DictReader: the last duplicate wins
-        need = std::max(need, col[k] + 1);
-    }
+    csv_columns(head, want, N_COLS, col);
+    for (int k = 0; k < N_COLS; ++k) need = std::max(need, col[k] + 1);
     const int64_t body = end - p;
     const bool quoted = memchr(p, '"', (size_t)body) != nullptr;
     for (int k = 0; k < N_COLS; ++k)
@@ -915,19 +893,9 @@ static int a2c_parse_csv(A2CState &S, const char *text, int64_t len, bool &use_p
         }
     int nt = quoted ? 1 : s2a_threads();
     if (body < (int64_t)nt * (1 << 20)) nt = (int)std::max<int64_t>(1, body >> 20);
+    const std::vector<const char *> cut = csv_cuts(p, end, nt);
     std::vector<A2CPart> parts(nt);
-    for (int t = 0; t < nt; ++t) {
-        const char *c0 = p + body * t / nt;
-        if (t) {
-            while (c0 < end && *c0 != '\n') ++c0;
-            if (c0 < end) ++c0;
-        }
-        parts[t].beg = c0;
-    }
-    for (int t = 0; t < nt; ++t) {
-        parts[t].end = t + 1 < nt ? parts[t + 1].beg : end;
-        if (parts[t].end < parts[t].beg) parts[t].end = parts[t].beg;
-    }
+    for (int t = 0; t < nt; ++t) { parts[t].beg = cut[t]; parts[t].end = cut[t + 1]; }
     if (quoted) {
         use_pool = true;
         a2c_parse_quoted(parts[0], col, need, S.cls, S.pool);

@@ -31,6 +31,7 @@
 #include "mh_fastq.h"
 #include "mh_gunzip.h"
 #include "mh_internal.h"
+#include "mh_prelim.h"
 #include "mh_sam.h"
 #include "mh_text.h"
 
@@ -2075,330 +2076,25 @@ int mh_rows_load(mh_ctx *ctx, int64_t n_rows, const int32_t *flag, const int32_t
     return load_reads(*c, R.reads, dummy, n_rows, 0, seq, qual, offsets, lens, false);
 }
 
-// ---- prelim.csv reader ------------------------------------------------------
-// std::atoi on a string_view (leading blanks and sign, then digits)
-static int sv_atoi(std::string_view v)
-{
-    size_t i = 0;
-    while (i < v.size() && (v[i] == ' ' || v[i] == '\t')) ++i;
-    bool neg = false;
-    if (i < v.size() && (v[i] == '-' || v[i] == '+')) neg = v[i++] == '-';
-    long long x = 0;
-    while (i < v.size() && v[i] >= '0' && v[i] <= '9') x = x * 10 + (v[i++] - '0');
-    return (int)(neg ? -x : x);
-}
-
-// csv.DictReader semantics for the 11 SAM columns prelim_map writes
-// (prelim_map.py:142-151), then remap.matchmaker (remap.py:853-889) over the
-// rows whose rname is in the @SQ set, then the rows go to the device.
-namespace mh {
-struct CsvRows {
-    std::vector<int32_t> flag, ref, pos, cig_off, n_cigar, maxm, name_id;
-    std::vector<uint32_t> cigar;
-    std::vector<uint8_t> seq, qual;
-    std::vector<int64_t> off;
-    std::vector<int32_t> len;
-    std::vector<int64_t> units;
-    std::vector<std::string> qnames_own;   // serial (quoted) path: owned names
-};
-
-}  // namespace mh
-
+// prelim.csv text (mh_prelim.cpp) -> rows; mh_rows_info hands back the rest
 extern "C" int mh_rows_load_csv(mh_ctx *ctx, const char *text, int64_t len, int n_refs,
                                 const char *const *refnames, int64_t *n_rows, int64_t *n_units,
                                 int32_t *n_present)
 {
     if (!ctx || !text || len < 0 || n_refs < 0) return -3;
     CtxEx *c = X(ctx);
-    std::unordered_map<std::string, int> refidx;
-    for (int r = 0; r < n_refs; ++r) refidx.emplace(refnames[r], r);
-    const char *p = text, *end = text + len;
-    std::vector<std::string> f;
-    if (!csv_record(p, end, f)) { set_error("prelim csv: empty"); return -3; }
-    const char *want[11] = {"qname", "flag", "rname", "pos", "mapq", "cigar", "rnext", "pnext",
-                            "tlen", "seq", "qual"};
-    int col[11];
-    for (int k = 0; k < 11; ++k) {
-        col[k] = -1;
-        for (size_t z = 0; z < f.size(); ++z) if (f[z] == want[k]) col[k] = (int)z;
-        if (col[k] < 0) { set_error("prelim csv: missing column %s", want[k]); return -3; }
-    }
-    CsvRows R;
-    std::vector<std::string_view> qnames;   // per row, into text
-    std::unordered_map<std::string, int> unknown;
-    std::vector<uint32_t> ops;
-    bool parallel_ok = true;
-    std::vector<std::deque<std::string>> pown;   // unescaped names (stable addresses; qnames views them)
-    {
-        // rows parsed on host threads in contiguous blocks cut at record
-        // ends (a newline outside quotes: the count of '"' before it is
-        // even), concatenated in order.  A record this parser does not take
-        // (a newline inside a quoted field, text after a closing quote)
-        // sends the whole file to the serial csv_record path below.
-        int ncol = 11;   // fields a row needs: up to the last column used
-        for (int k = 0; k < 11; ++k) ncol = std::max(ncol, col[k] + 1);
-        const int64_t bytes = end - p;
-        const int nt = std::max(1, std::min(s2a_threads(), (int)(bytes >> 22) + 1));
-        std::vector<const char *> cut(nt + 1);
-        cut[0] = p;
-        cut[nt] = end;
-        for (int t = 1; t < nt; ++t) {
-            const char *q = p + bytes * t / nt;
-            if (q < cut[t - 1]) q = cut[t - 1];
-            const char *nl = (const char *)std::memchr(q, '\n', (size_t)(end - q));
-            cut[t] = nl ? nl + 1 : end;
-        }
-        std::vector<int64_t> nq(nt, 0);
-        par_for(nt, [&](int t) {
-            int64_t k = 0;
-            for (const char *q = cut[t]; q < cut[t + 1]; ++q) k += *q == '"';
-            nq[t] = k;
-        });
-        int64_t par = 0;
-        for (int t = 1; t < nt; ++t) {
-            par += nq[t - 1];
-            if (par & 1) {   // this cut is inside a quoted field: move it on
-                const char *q = cut[t];
-                int64_t seen = 0;
-                while (q < end && !(*q == '\n' && ((par + seen) & 1) == 0)) seen += *q++ == '"';
-                cut[t] = q < end ? q + 1 : end;
-                if (cut[t] > cut[t + 1]) cut[t + 1] = cut[t];
-                par += seen;
-                nq[t] -= seen;
-            }
-        }
-        std::vector<CsvRows> part(nt);
-        std::vector<std::vector<std::string_view>> pq(nt);
-        std::vector<std::vector<std::string>> punk(nt);
-        pown.resize(nt);
-        std::vector<int> bad(nt, 0);
-        par_for(nt, [&](int t) {
-            CsvRows &P = part[t];
-            std::vector<uint32_t> lops;
-            std::vector<std::string_view> fv;
-            std::vector<char> fe;   // field holds "" escapes
-            std::string tmp, last_rname = "\x01", cig, seqv;
-            int last_ref = -1;
-            P.flag.reserve((size_t)((cut[t + 1] - cut[t]) / 500 + 16));
-            auto value = [&](size_t i) -> std::string_view {   // unescaped view (tmp may back it)
-                if (!fe[i]) return fv[i];
-                tmp.clear();
-                for (size_t x = 0; x < fv[i].size(); ++x) {
-                    tmp.push_back(fv[i][x]);
-                    if (fv[i][x] == '"') ++x;
-                }
-                return std::string_view(tmp);
-            };
-            const char *q = cut[t], *e = cut[t + 1];
-            while (q < e) {
-                const char *nl = (const char *)std::memchr(q, '\n', (size_t)(e - q));
-                const char *le = nl ? nl : e;
-                const char *next = nl ? nl + 1 : e;
-                if (le > q && le[-1] == '\r') --le;
-                fv.clear();
-                fe.clear();
-                for (const char *s0 = q;;) {
-                    if (s0 < le && *s0 == '"') {
-                        const char *c0 = s0 + 1, *x = c0;
-                        bool esc = false, closed = false;
-                        while (x < le) {
-                            if (*x == '"') {
-                                if (x + 1 < le && x[1] == '"') { esc = true; x += 2; continue; }
-                                closed = true;
-                                break;
-                            }
-                            ++x;
-                        }
-                        if (!closed || (x + 1 < le && x[1] != ',')) { bad[t] = 1; return; }
-                        fv.emplace_back(c0, (size_t)(x - c0));
-                        fe.push_back(esc);
-                        if (x + 1 >= le) break;
-                        s0 = x + 2;
-                        continue;
-                    }
-                    const char *cm = (const char *)std::memchr(s0, ',', (size_t)(le - s0));
-                    if (!cm) { fv.emplace_back(s0, (size_t)(le - s0)); fe.push_back(0); break; }
-                    fv.emplace_back(s0, (size_t)(cm - s0));
-                    fe.push_back(0);
-                    s0 = cm + 1;
-                }
-                q = next;
-                if (fv.size() == 1 && fv[0].empty()) continue;
-                if ((int)fv.size() < ncol) { bad[t] = 2; return; }
-                // rows come grouped by rname: look a name up only when it changes
-                const std::string_view rn = value(col[2]);
-                if (rn != last_rname) {
-                    last_rname.assign(rn.data(), rn.size());
-                    auto it = refidx.find(last_rname);
-                    last_ref = it == refidx.end() ? -1 : it->second;
-                }
-                const int ref = last_ref;
-                const int flag = sv_atoi(value(col[1]));
-                int maxm = 0;
-                P.cig_off.push_back((int32_t)P.cigar.size());
-                if (!(flag & 4)) {
-                    cig.assign(value(col[5]));
-                    if (!parse_cigar_ops(cig, lops, maxm)) lops.assign(1, 3u);
-                    if (lops.size() > MH_MAXOPS) lops.assign(1, 3u);
-                } else {
-                    lops.clear();
-                }
-                P.cigar.insert(P.cigar.end(), lops.begin(), lops.end());
-                P.n_cigar.push_back((int32_t)lops.size());
-                P.flag.push_back(flag);
-                P.ref.push_back(ref);
-                P.name_id.push_back(ref);
-                P.pos.push_back(sv_atoi(value(col[3])));
-                P.maxm.push_back(maxm);
-                seqv.assign(value(col[9]));   // (escapes are possible in principle)
-                const std::string_view quals = value(col[10]);
-                P.off.push_back((int64_t)P.seq.size());
-                P.len.push_back((int32_t)seqv.size());
-                P.seq.insert(P.seq.end(), seqv.begin(), seqv.end());
-                const size_t nqk = std::min(quals.size(), seqv.size());
-                P.qual.insert(P.qual.end(), quals.begin(), quals.begin() + nqk);
-                P.qual.insert(P.qual.end(), seqv.size() - nqk, 'J');
-                if (fe[col[0]]) {
-                    pown[t].emplace_back(value(col[0]));
-                    pq[t].emplace_back(pown[t].back());
-                } else {
-                    pq[t].push_back(fv[col[0]]);
-                }
-                punk[t].push_back(ref < 0 ? last_rname : std::string());
-            }
-        });
-        for (int t = 0; t < nt; ++t)
-            if (bad[t] == 1) parallel_ok = false;
-        if (parallel_ok)
-            for (int t = 0; t < nt; ++t)
-                if (bad[t] == 2) { set_error("prelim csv: short row"); return -3; }
-        if (parallel_ok) {
-            // sizes, then every part copied to its place on its own thread
-            std::vector<int64_t> rb(nt + 1, 0), cb(nt + 1, 0), sb(nt + 1, 0);
-            for (int t = 0; t < nt; ++t) {
-                rb[t + 1] = rb[t] + (int64_t)part[t].flag.size();
-                cb[t + 1] = cb[t] + (int64_t)part[t].cigar.size();
-                sb[t + 1] = sb[t] + (int64_t)part[t].seq.size();
-            }
-            const int64_t nrw = rb[nt];
-            R.flag.resize(nrw); R.ref.resize(nrw); R.pos.resize(nrw); R.cig_off.resize(nrw);
-            R.n_cigar.resize(nrw); R.maxm.resize(nrw); R.name_id.resize(nrw); R.off.resize(nrw);
-            R.len.resize(nrw); R.cigar.resize(cb[nt]); R.seq.resize(sb[nt]); R.qual.resize(sb[nt]);
-            qnames.resize(nrw);
-            for (int t = 0; t < nt; ++t)   // '*' and other names outside @SQ, ids in first-seen order
-                for (size_t i = 0; i < part[t].flag.size(); ++i)
-                    if (part[t].ref[i] < 0) {
-                        auto u = unknown.emplace(punk[t][i], (int)unknown.size());
-                        part[t].name_id[i] = -1 - u.first->second;
-                    }
-            par_for(nt, [&](int t) {
-                const CsvRows &P = part[t];
-                const size_t n0 = P.flag.size(), r0 = (size_t)rb[t];
-                std::copy(P.flag.begin(), P.flag.end(), R.flag.begin() + r0);
-                std::copy(P.ref.begin(), P.ref.end(), R.ref.begin() + r0);
-                std::copy(P.pos.begin(), P.pos.end(), R.pos.begin() + r0);
-                std::copy(P.n_cigar.begin(), P.n_cigar.end(), R.n_cigar.begin() + r0);
-                std::copy(P.maxm.begin(), P.maxm.end(), R.maxm.begin() + r0);
-                std::copy(P.name_id.begin(), P.name_id.end(), R.name_id.begin() + r0);
-                std::copy(P.len.begin(), P.len.end(), R.len.begin() + r0);
-                for (size_t i = 0; i < n0; ++i) {
-                    R.cig_off[r0 + i] = P.cig_off[i] + (int32_t)cb[t];
-                    R.off[r0 + i] = P.off[i] + sb[t];
-                }
-                std::copy(P.cigar.begin(), P.cigar.end(), R.cigar.begin() + cb[t]);
-                std::copy(P.seq.begin(), P.seq.end(), R.seq.begin() + sb[t]);
-                std::copy(P.qual.begin(), P.qual.end(), R.qual.begin() + sb[t]);
-                std::copy(pq[t].begin(), pq[t].end(), qnames.begin() + r0);
-            });
-        }
-    }
-    if (!parallel_ok) {
-        while (csv_record(p, end, f)) {
-            if (f.size() == 1 && f[0].empty()) continue;
-            if ((int)f.size() < 11) { set_error("prelim csv: short row"); return -3; }
-            const std::string &rname = f[col[2]], &seqs = f[col[9]], &quals = f[col[10]];
-            const int flag = std::atoi(f[col[1]].c_str());
-            auto it = refidx.find(rname);
-            int ref = it == refidx.end() ? -1 : it->second;
-            int nid = ref;
-            if (ref < 0) {
-                auto u = unknown.emplace(rname, (int)unknown.size());
-                nid = -1 - u.first->second;   // '*' and other names outside @SQ
-            }
-            int maxm = 0;
-            R.cig_off.push_back((int32_t)R.cigar.size());
-            if (!(flag & 4)) {
-                if (!parse_cigar_ops(f[col[5]], ops, maxm)) ops.assign(1, 3u);  // invalid: fails if used
-                if (ops.size() > MH_MAXOPS) ops.assign(1, 3u);
-            } else {
-                ops.clear();
-            }
-            R.cigar.insert(R.cigar.end(), ops.begin(), ops.end());
-            R.n_cigar.push_back((int32_t)ops.size());
-            R.flag.push_back(flag);
-            R.ref.push_back(ref);
-            R.name_id.push_back(nid);
-            R.pos.push_back(std::atoi(f[col[3]].c_str()));
-            R.maxm.push_back(maxm);
-            R.off.push_back((int64_t)R.seq.size());
-            R.len.push_back((int32_t)seqs.size());
-            R.seq.insert(R.seq.end(), seqs.begin(), seqs.end());
-            std::string q = quals;
-            q.resize(seqs.size(), 'J');
-            R.qual.insert(R.qual.end(), q.begin(), q.end());
-            R.qnames_own.push_back(f[col[0]]);
-        }
-        for (const std::string &x : R.qnames_own) qnames.emplace_back(x);
-    }
-    // matchmaker (remap.py:853-889) over the rows whose rname is in @SQ
-    const int64_t nrow = (int64_t)R.flag.size();
-    std::unordered_map<std::string_view, int64_t> pending;   // qname -> slot in order
-    pending.reserve((size_t)nrow);
-    std::vector<std::pair<int64_t, bool>> order;             // (row, alive) insertion order
-    order.reserve((size_t)nrow);
-    for (int64_t row = 0; row < nrow; ++row) {
-        if (R.ref[row] < 0) continue;
-        const std::string_view qname = qnames[row];
-        auto pit = pending.find(qname);
-        if (pit == pending.end()) {
-            pending.emplace(qname, (int64_t)order.size());
-            order.push_back({row, true});
-        } else {
-            order[pit->second].second = false;
-            R.units.push_back(order[pit->second].first);
-            R.units.push_back(row);
-            pending.erase(pit);
-        }
-    }
-    for (auto &o : order) if (o.second) { R.units.push_back(o.first); R.units.push_back(-1); }
-    const int64_t nr = (int64_t)R.flag.size();
-    const int64_t nu = (int64_t)R.units.size() / 2;
-    // compact reference ids: only references some unit row names, in @SQ
-    // order (keeps the dense counters small); rows outside @SQ are never
-    // paired and get compact id 0 (unused)
-    std::vector<int32_t> used(n_refs > 0 ? n_refs : 1, 0);
-    for (int64_t k = 0; k < 2 * nu; ++k) if (R.units[k] >= 0) used[R.ref[R.units[k]]] = 1;
-    std::vector<int32_t> compact(n_refs > 0 ? n_refs : 1, -1);
-    c->csv_present.clear();
-    for (int r = 0; r < n_refs; ++r)
-        if (used[r]) { compact[r] = (int32_t)c->csv_present.size(); c->csv_present.push_back(r); }
-    std::vector<int32_t> dref(R.ref);
-    for (auto &x : dref) x = (x >= 0 && compact[x] >= 0) ? compact[x] : 0;
-    c->csv_unknown.assign(unknown.size(), std::string());
-    for (auto &kv : unknown) c->csv_unknown[kv.second] = kv.first;
-    int st = mh_rows_load(ctx, nr, R.flag.data(), dref.data(), R.pos.data(), R.cig_off.data(),
+    PrelimRows R;
+    std::string err;
+    if (int st = prelim_parse(text, len, n_refs, refnames, 0, R, err)) { set_error("%s", err.c_str()); return st; }
+    const int64_t nr = (int64_t)R.flag.size(), nu = (int64_t)R.units.size() / 2;
+    int st = mh_rows_load(ctx, nr, R.flag.data(), R.ref.data(), R.pos.data(), R.cig_off.data(),
                           R.n_cigar.data(), R.cigar.empty() ? nullptr : R.cigar.data(),
                           R.seq.data(), R.qual.data(), R.off.data(), R.len.data(), nu,
                           R.units.data());
     if (st) return st;
-    c->csv_rows_info.clear();
-    c->csv_rows_info.reserve(nr * 4);
-    for (int64_t i = 0; i < nr; ++i) {
-        c->csv_rows_info.push_back(R.name_id[i]);
-        c->csv_rows_info.push_back(R.flag[i]);
-        c->csv_rows_info.push_back(R.maxm[i]);
-        c->csv_rows_info.push_back(dref[i]);
-    }
+    c->csv_rows_info.swap(R.info);
+    c->csv_present.swap(R.present);
+    c->csv_unknown.swap(R.unknown);
     if (n_rows) *n_rows = nr;
     if (n_units) *n_units = nu;
     if (n_present) *n_present = (int32_t)c->csv_present.size();

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <exception>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -307,6 +308,17 @@ void par_for(int nt, const std::function<void(int)> &fn)
     guarded(0);
     for (auto &x : th) x.join();
     if (first) std::rethrow_exception(first);
+}
+
+int s2a_threads()
+{
+    int n = (int)std::thread::hardware_concurrency();
+    if (const char *e = getenv("OMP_NUM_THREADS")) {
+        const int v = atoi(e);
+        if (v > 0 && v < n) n = v;
+    }
+    if (n < 1) n = 1;
+    return n > 16 ? 16 : n;
 }
 
 double ms_since(std::chrono::steady_clock::time_point t)

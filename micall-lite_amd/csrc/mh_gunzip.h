@@ -21,7 +21,7 @@ namespace mh {
 // process).  When a thread cannot be created the remaining indices run on
 // the caller.
 void par_for(int nt, const std::function<void(int)> &fn);
-// host worker count: min(16, hardware threads, OMP_NUM_THREADS) (mh_s2a_host.cpp)
+// host worker count: min(16, hardware threads, OMP_NUM_THREADS)
 int s2a_threads();
 // milliseconds since t
 double ms_since(std::chrono::steady_clock::time_point t);

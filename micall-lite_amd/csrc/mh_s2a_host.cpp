@@ -19,8 +19,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -32,73 +34,7 @@ namespace mh {
 
 static const char *const S2A_CAUSE[] = {"", "unmatched", "badCigar", "2refs", "manyNs", ""};
 
-int s2a_threads()
-{
-    int n = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("OMP_NUM_THREADS")) {
-        const int v = atoi(e);
-        if (v > 0 && v < n) n = v;
-    }
-    if (n < 1) n = 1;
-    return n > 16 ? 16 : n;
-}
-
-struct FieldRef {
-    const char *p;
-    size_t n;
-};
-
-constexpr int MAXCOLS = 64;
-
-// one CSV record as views (quoted fields unescaped into scratch[k]); same
-// dialect as csv_record (mh_text.h)
-static bool record_views(const char *&p, const char *end, std::vector<FieldRef> &f,
-                         std::vector<std::string> &scratch)
-{
-    f.clear();
-    if (p >= end) return false;
-    for (size_t k = 0;; ++k) {
-        if (k >= (size_t)MAXCOLS) return false;
-        if (p < end && *p == '"') {
-            std::string &s = scratch[k];
-            s.clear();
-            ++p;
-            while (p < end) {
-                if (*p == '"') {
-                    if (p + 1 < end && p[1] == '"') { s.push_back('"'); p += 2; continue; }
-                    ++p;
-                    break;
-                }
-                s.push_back(*p++);
-            }
-            while (p < end && *p != ',' && *p != '\n' && *p != '\r') s.push_back(*p++);
-            f.push_back({s.data(), s.size()});
-        } else {
-            const char *q = p;
-            while (p < end && *p != ',' && *p != '\n' && *p != '\r') ++p;
-            f.push_back({q, (size_t)(p - q)});
-        }
-        if (p < end && *p == ',') { ++p; continue; }
-        if (p < end && *p == '\r') ++p;
-        if (p < end && *p == '\n') ++p;
-        return true;
-    }
-}
-
-// Python int() on a CSV field: optional surrounding whitespace and sign
-static bool py_int(const FieldRef &f, int32_t &v)
-{
-    const char *a = f.p, *b = f.p + f.n;
-    while (a < b && (*a == ' ' || *a == '\t')) ++a;
-    while (b > a && (b[-1] == ' ' || b[-1] == '\t')) --b;
-    if (a < b && *a == '+') ++a;
-    if (a == b) return false;
-    long long x = 0;
-    auto r = std::from_chars(a, b, x);
-    if (r.ec != std::errc() || r.ptr != b || x < INT32_MIN || x > INT32_MAX) return false;
-    v = (int32_t)x;
-    return true;
-}
+constexpr int MAXCOLS = 64;   // columns a remap.csv record may have
 
 static uint64_t hash_bytes(const char *p, size_t n)
 {
@@ -156,8 +92,8 @@ struct Part {
 
 static void parse_part(Part &P, const int *col)
 {
-    std::vector<FieldRef> f;
-    std::vector<std::string> scratch(MAXCOLS);
+    std::vector<std::string_view> f;
+    std::deque<std::string> scratch;
     std::unordered_map<std::string, int> rmap;
     std::vector<uint32_t> ops;
     const char *p = P.beg;
@@ -176,52 +112,52 @@ static void parse_part(Part &P, const int *col)
         P.cig_off.reserve(rows); P.n_cig.reserve(rows); P.rid.reserve(rows); P.qhash.reserve(rows);
         P.cstate.reserve(rows); P.qshort.reserve(rows);
     }
-    while (p < P.end) {
-        if (!record_views(p, P.end, f, scratch)) {
+    while (csv_views(p, P.end, f, scratch)) {
+        if (f.size() > (size_t)MAXCOLS) {
             P.err = 1; P.err_row = P.rows; P.err_msg = "more than 64 columns";
             return;
         }
-        if (f.size() == 1 && f[0].n == 0) continue;          // blank line
+        if (f.size() == 1 && f[0].empty()) continue;          // blank line
         if ((int)f.size() < need) {
             P.err = 1; P.err_row = P.rows; P.err_msg = "short row";
             return;
         }
-        const FieldRef &q = f[col[0]], &rn = f[col[2]], &cg = f[col[5]], &sq = f[col[9]],
-                       &ql = f[col[10]];
+        const std::string_view q = f[col[0]], rn = f[col[2]], cg = f[col[5]], sq = f[col[9]],
+                               ql = f[col[10]];
         int32_t fl = 0, ps = 0;
-        if (!py_int(f[col[1]], fl)) {
+        if (!py_int32(f[col[1]], fl)) {
             P.err = 1; P.err_row = P.rows; P.err_msg = "flag is not an integer";
             return;
         }
         P.flag.push_back(fl);
-        P.pos.push_back(py_int(f[col[3]], ps) ? ps : INT32_MIN);
+        P.pos.push_back(py_int32(f[col[3]], ps) ? ps : INT32_MIN);
         P.qoff.push_back((int64_t)P.qpool.size());
-        P.qlen.push_back((int32_t)q.n);
-        P.qpool.append(q.p, q.n);
-        P.qhash.push_back(hash_bytes(q.p, q.n));
-        auto it = rmap.find(std::string(rn.p, rn.n));
+        P.qlen.push_back((int32_t)q.size());
+        P.qpool.append(q.data(), q.size());
+        P.qhash.push_back(hash_bytes(q.data(), q.size()));
+        auto it = rmap.find(std::string(rn));
         if (it == rmap.end()) {
-            it = rmap.emplace(std::string(rn.p, rn.n), (int)P.rnames.size()).first;
-            P.rnames.emplace_back(rn.p, rn.n);
+            it = rmap.emplace(std::string(rn), (int)P.rnames.size()).first;
+            P.rnames.emplace_back(rn);
         }
         P.rid.push_back(it->second);
         P.coff.push_back((int64_t)P.cpool.size());
-        P.clen.push_back((int32_t)cg.n);
-        P.cpool.append(cg.p, cg.n);
-        P.cstate.push_back(cigar_ops(cg.p, cg.n, (int64_t)sq.n, ops));
+        P.clen.push_back((int32_t)cg.size());
+        P.cpool.append(cg.data(), cg.size());
+        P.cstate.push_back(cigar_ops(cg.data(), cg.size(), (int64_t)sq.size(), ops));
         P.cig_off.push_back((int32_t)P.cig.size());
         P.n_cig.push_back(P.cstate.back() == CIG_OK ? (int32_t)ops.size() : 0);
         if (P.cstate.back() == CIG_OK) P.cig.insert(P.cig.end(), ops.begin(), ops.end());
         P.soff.push_back((int64_t)P.seq.size());
-        P.slen.push_back((int32_t)sq.n);
-        P.seq.append(sq.p, sq.n);
-        P.qshort.push_back(ql.n < sq.n);
-        if (ql.n >= sq.n) P.qual.append(ql.p, sq.n);
+        P.slen.push_back((int32_t)sq.size());
+        P.seq.append(sq.data(), sq.size());
+        P.qshort.push_back(ql.size() < sq.size());
+        if (ql.size() >= sq.size()) P.qual.append(ql.data(), sq.size());
         else {
-            P.qual.append(ql.p, ql.n);
+            P.qual.append(ql.data(), ql.size());
             const size_t at = P.qual.size();
-            P.qual.resize(at + (sq.n - ql.n));
-            memset(P.qual.data() + at, '!', sq.n - ql.n);
+            P.qual.resize(at + (sq.size() - ql.size()));
+            memset(P.qual.data() + at, '!', sq.size() - ql.size());
         }
         ++P.rows;
     }
@@ -290,38 +226,18 @@ int s2a_parse(S2AState &S, const char *text, int64_t len, int64_t body_lo, int64
     const char *want[11] = {"qname", "flag", "rname", "pos", "mapq", "cigar", "rnext", "pnext",
                             "tlen", "seq", "qual"};
     int col[11];
-    for (int k = 0; k < 11; ++k) {
-        col[k] = -1;
-        for (size_t z = 0; z < head.size(); ++z) if (head[z] == want[k]) col[k] = (int)z;
+    csv_columns(head, want, 11, col);
+    for (int k = 0; k < 11; ++k)
         if (col[k] < 0) {
             if (k == 4 || k == 6 || k == 7 || k == 8) { col[k] = 0; continue; }   // unused
             set_error("remap csv: missing column %s", want[k]);
             return -3;
         }
-    }
-    // ---- split the body at record boundaries: '\n' outside quotes ----
+    // ---- split the body at record ends ----
     const int64_t body = end - p;
     int nt = s2a_threads();
     if (body < (int64_t)nt * (1 << 20)) nt = (int)std::max<int64_t>(1, body >> 20);
-    std::vector<const char *> cut(nt + 1, p);
-    cut[nt] = end;
-    for (int t = 1; t < nt; ++t) {
-        const char *c = p + body * t / nt;
-        while (c < end && *c != '\n') ++c;
-        cut[t] = c < end ? c + 1 : end;
-        if (cut[t] < cut[t - 1]) cut[t] = cut[t - 1];
-    }
-    std::vector<int64_t> quotes(nt, 0);
-    par_for(nt, [&](int t) {
-        int64_t n = 0;
-        for (const char *c = cut[t]; c < cut[t + 1]; ++c) n += *c == '"';
-        quotes[t] = n;
-    });
-    int64_t par = 0;
-    for (int t = 0; t + 1 < nt; ++t) {
-        par += quotes[t];
-        if (par & 1) { nt = 1; cut.assign({p, end}); break; }   // a boundary inside quotes
-    }
+    const std::vector<const char *> cut = csv_cuts(p, end, nt);
     std::vector<Part> parts(nt);
     for (int t = 0; t < nt; ++t) { parts[t].beg = cut[t]; parts[t].end = cut[t + 1]; }
     s2a_mark(tp, "split");

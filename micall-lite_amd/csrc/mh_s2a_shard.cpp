@@ -535,8 +535,9 @@ extern "C" int mh_sam2aln_part(mh_ctx *ctx, int fd, int part, int parts, int q_c
         const char *p = text, *end = text + len;
         std::vector<std::string> head;
         if (!csv_record(p, end, head)) { set_error("remap csv: empty"); return -3; }
+        const char *const want = "qname";
         int qcol = -1;
-        for (size_t k = 0; k < head.size(); ++k) if (head[k] == "qname") qcol = (int)k;
+        csv_columns(head, &want, 1, &qcol);
         if (qcol < 0) return 1;
         const int64_t lo = p - text, hi = (int64_t)len;
         S2AShard &H = s2a_shard(S);

@@ -1,7 +1,7 @@
 // mh_sam.cpp -- SAM text to pileup rows on the host: remap.matchmaker
 // (micall/core/remap.py:853-889) with include_singles=True, then the fields
 // merge_reads uses (remap.py:86-126).  Plain C++, no device part: it is also
-// compiled alone, with the sanitizers, by tests/test_sam_parse_host.py.
+// compiled alone, with the sanitizers, by tests/test_debug_reports_host.py.
 #include "mh_sam.h"
 
 #include <cstdarg>
@@ -14,26 +14,6 @@
 namespace mh {
 
 void set_error(const char *fmt, ...);
-
-// int(text) for FLAG / POS: blanks around an optional sign and digits
-static bool sam_int(std::string_view v, int32_t &out)
-{
-    auto blank = [](char ch) { return ch == ' ' || ch == '\r' || ch == '\n' || ch == '\f' || ch == '\v'; };
-    size_t a = 0, b = v.size();
-    while (a < b && blank(v[a])) ++a;
-    while (b > a && blank(v[b - 1])) --b;
-    bool neg = false;
-    if (a < b && (v[a] == '-' || v[a] == '+')) neg = v[a++] == '-';
-    if (a == b) return false;
-    int64_t x = 0;
-    for (; a < b; ++a) {
-        if (v[a] < '0' || v[a] > '9') return false;
-        x = x * 10 + (v[a] - '0');
-        if (x > INT32_MAX) return false;
-    }
-    out = (int32_t)(neg ? -x : x);
-    return true;
-}
 
 static int fail(std::string &err, int64_t line, const char *what)
 {
@@ -50,8 +30,6 @@ int sam_parse(const char *text, int64_t len, SamRows &R, std::string &err)
     };
     std::vector<Row> rows;                                   // kept rows in line order
     std::unordered_map<std::string_view, int32_t> refidx;    // views into text
-    std::unordered_map<std::string_view, int64_t> pending;   // qname -> slot in order
-    std::vector<std::pair<int64_t, bool>> order;             // (row, still single)
     std::vector<int64_t> units;                              // row numbers in line order
     std::vector<std::string_view> f;
     const char *p = text, *end = text + (len > 0 ? len : 0);
@@ -87,30 +65,18 @@ int sam_parse(const char *text, int64_t len, SamRows &R, std::string &err)
         Row r;
         r.qname = f[0];
         r.ref = hit->second;
-        if (!sam_int(f[1], r.flag)) return fail(err, line_no, "FLAG is not an integer");
-        if (!sam_int(f[3], r.pos)) return fail(err, line_no, "POS is not an integer");
+        if (!py_int32(f[1], r.flag)) return fail(err, line_no, "FLAG is not an integer");
+        if (!py_int32(f[3], r.pos)) return fail(err, line_no, "POS is not an integer");
         r.cigar = f[5];
         r.seq = f[9];
         r.qual = f[10];
-        const int64_t row = (int64_t)rows.size();
         rows.push_back(r);
-        const auto pit = pending.find(r.qname);
-        if (pit == pending.end()) {
-            pending.emplace(r.qname, (int64_t)order.size());
-            order.push_back({row, true});
-        } else {
-            order[(size_t)pit->second].second = false;
-            units.push_back(order[(size_t)pit->second].first);
-            units.push_back(row);
-            pending.erase(pit);
-        }
     }
-    for (const auto &o : order)
-        if (o.second) { units.push_back(o.first); units.push_back(-1); }
+    matchmake((int64_t)rows.size(), [&](int64_t row) { return rows[(size_t)row].qname; },
+              [](int64_t) { return true; }, units);
     // rows renumbered in unit order
     R.ends.assign(R.names.size(), 0);
     std::vector<uint32_t> ops;
-    std::string cig;
     for (const int64_t src : units) {
         if (src < 0) { R.units.push_back(-1); continue; }
         const Row &r = rows[(size_t)src];
@@ -122,8 +88,7 @@ int sam_parse(const char *text, int64_t len, SamRows &R, std::string &err)
         int maxm = 0;
         ops.clear();
         if (!(r.flag & 4)) {
-            cig.assign(r.cigar);
-            if (!parse_cigar_ops(cig, ops, maxm) || ops.size() > MH_MAXOPS) ops.assign(1, 3u);
+            if (!parse_cigar_ops(r.cigar, ops, maxm) || ops.size() > MH_MAXOPS) ops.assign(1, 3u);
             int64_t span = 0;
             for (const uint32_t w : ops)
                 if ((w & 15) == MH_OP_M || (w & 15) == MH_OP_D) span += w >> 4;

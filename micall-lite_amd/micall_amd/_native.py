@@ -103,6 +103,9 @@ def _declare(L):
         'mh_sam_info': ([_P, ctypes.c_char_p, ctypes.c_size_t, _P], ctypes.c_int),
         'mh_sam_parse': ([ctypes.c_char_p, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                           _P, _P, ctypes.c_char_p, _P], ctypes.c_int),
+        'mh_prelim_parse': ([ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
+                             ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                             ctypes.c_char_p], ctypes.c_int),
         'mh_pileup_watch': ([_P, ctypes.c_int, _P, _P], ctypes.c_int),
         'mh_pileup_watch_fetch': ([_P, _P, _P], ctypes.c_int),
         'mh_pileup': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P], ctypes.c_int),
@@ -364,6 +367,42 @@ def sam_parse(text):
     args = (flag[:n], ref[:n], pos[:n], cig_off[:n], n_cig[:n], cigar[:nc], seq[:nb], qual[:nb],
             offs[:n], lens[:n], units[:2 * sz.n_units])
     return names.value.decode().split('\n')[:-1], ends[:sz.n_refs], args
+
+
+class _PrelimSizes(ctypes.Structure):
+    _fields_ = [('n_rows', ctypes.c_int64), ('n_units', ctypes.c_int64), ('n_cigar', ctypes.c_int64),
+                ('n_bases', ctypes.c_int64), ('n_present', ctypes.c_int32),
+                ('unknown_bytes', ctypes.c_size_t)]
+
+
+def prelim_parse(text, refnames, threads=0):
+    """mh_prelim_parse: prelim.csv text parsed on the host as
+    mh_rows_load_csv parses it, no device; threads cuts the text into that
+    many blocks (0: the default).  Returns (rows_load arguments, info): the
+    eleven arrays Context.rows_load takes and what Context.rows_load_csv
+    returns, dict(n_rows, n_units, info, present, unknown)."""
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    names = (ctypes.c_char_p * max(len(refnames), 1))(*[r.encode() for r in refnames])
+    sz = _PrelimSizes()
+    head = (data, len(data), len(refnames), names, threads, ctypes.byref(sz))
+    check(lib().mh_prelim_parse(*head, *([None] * 14)), 'mh_prelim_parse')
+    n, nc, nb = sz.n_rows, sz.n_cigar, sz.n_bases
+    i32 = lambda k: np.zeros(max(k, 1), dtype=np.int32)
+    flag, ref, pos, cig_off, n_cig, lens = (i32(n) for _ in range(6))
+    cigar = np.zeros(max(nc, 1), dtype=np.uint32)
+    offs = np.zeros(max(n, 1), dtype=np.int64)
+    seq, qual = np.zeros(max(nb, 1), dtype=np.uint8), np.zeros(max(nb, 1), dtype=np.uint8)
+    units = np.zeros(max(2 * sz.n_units, 1), dtype=np.int64)
+    info, present = i32(4 * n), i32(sz.n_present)
+    unknown = ctypes.create_string_buffer(sz.unknown_bytes + 1)
+    check(lib().mh_prelim_parse(*head, _ptr(flag), _ptr(ref), _ptr(pos), _ptr(cig_off), _ptr(n_cig),
+                                _ptr(cigar), _ptr(offs), _ptr(lens), _ptr(seq), _ptr(qual),
+                                _ptr(units), _ptr(info), _ptr(present), unknown), 'mh_prelim_parse')
+    args = (flag[:n], ref[:n], pos[:n], cig_off[:n], n_cig[:n], cigar[:nc], seq[:nb], qual[:nb],
+            offs[:n], lens[:n], units[:2 * sz.n_units])
+    return args, dict(n_rows=n, n_units=sz.n_units, info=info[:4 * n].reshape(n, 4),
+                      present=present[:sz.n_present],
+                      unknown=unknown.value.decode().split('\n')[:-1])
 
 
 def pileup_info(handle=None, n_refs=0):
