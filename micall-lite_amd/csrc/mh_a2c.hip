@@ -25,17 +25,22 @@
 //   k_a2c_ins_*   the read loop of InsertionWriter.write (:786-795): per
 //                 (insert range, row) the framed slice [3 left, 3 right) of
 //                 the read, rejected when it starts in the padding, holds '-'
-//                 or 'n' or no whole codon, and translated; equal amino-acid
-//                 strings of one range are grouped in an open-addressing
-//                 table (count, first row), every member is compared with
-//                 its group's first row (a collision is an error, never a
-//                 merge) and the distinct strings are gathered for the host.
+//                 or 'n' or no whole codon, and translated (k_a2c_ins_hash:
+//                 a key per pair); every member of a group of equal strings
+//                 is compared with the group's first row (k_a2c_ins_verify:
+//                 a collision is an error, never a merge) and the distinct
+//                 strings are gathered for the host (k_a2c_ins_gather).
 //   k_a2c_var_*   the nucleotide variants of the coordinate regions (the loop
 //                 of :346-375, the report of :537-549): per (region, row) the
-//                 padded row clipped to the region's window, equal clipped
-//                 sequences grouped the same way, and each region's greatest
-//                 by (count, sequence) picked on the device (see the section
-//                 at the end of this file).
+//                 padded row clipped to the region's window, hashed, verified
+//                 and gathered a wavefront per pair, and each region's
+//                 greatest by (count, sequence) picked on the device (see
+//                 the section at the end of this file).
+//   k_a2c_tab_count, k_a2c_tab_compact
+//                 the grouping both of them share (A2CTable): the keyed
+//                 pairs of a call in an open-addressing table, per distinct
+//                 key the summed count and the first row, then the occupied
+//                 slots as entries.  a2c_group_strings is its host side.
 // Host half (below the kernels): aligned.csv as csv.DictReader reads it,
 // consecutive (refname, qcut) groups (itertools.groupby, :884-887), the
 // codon extent of every frame, the bin lists.
@@ -47,6 +52,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -86,19 +92,14 @@ struct A2CChunk {
     int64_t beg, end;  // slice of bin_rows
 };
 
-struct A2CEntry {
-    int32_t range;
-    uint32_t first;
-    int32_t n_codons;
-    int32_t lo;        // slice start in the first row
-    unsigned long long count;
-};
-
-// One distinct clipped sequence of a coordinate region (mh_a2c_variants).
-struct A2CVarEntry {
-    int32_t region;    // index among the call's regions with a cut above 0
-    uint32_t first;    // first row of the group (0-based) that read it
-    int32_t len;       // bytes of the clipped sequence
+// One distinct string of a class: an amino-acid string of an insert range
+// (mh_a2c_inserts), a clipped sequence of a coordinate region
+// (mh_a2c_variants).
+struct A2CDistinct {
+    int32_t cls;       // the range; the index among the call's regions with a cut above 0
+    uint32_t first;    // first row that produced it: on the device its index among the
+                       // call's rows, in A2CState::entries its number within the group
+    int32_t len;       // codons of the amino-acid string; bytes of the clipped sequence
     int32_t pad;
     unsigned long long count;
 };
@@ -128,12 +129,12 @@ struct A2CState {
     int32_t *d_order = nullptr, *d_gfirst = nullptr, *d_gbin0 = nullptr, *d_ncod = nullptr;
     unsigned long long *d_bstart = nullptr, *d_bcur = nullptr;
     // insertion strings of the last mh_a2c_inserts, in (range, first row) order
-    std::vector<A2CEntry> entries;
+    std::vector<A2CDistinct> entries;
     std::string aminos;                       // one line per entry
     std::string ins_rows;                     // mh_a2c_insert_rows text (size query, then copy)
     std::unordered_map<const void *, size_t> dcap;   // bytes behind each device pointer (grow-only)
     // kept variants of the last mh_a2c_variants, in report order
-    std::vector<A2CVarEntry> var_entries;
+    std::vector<A2CDistinct> var_entries;
     std::vector<int32_t> var_region;          // the caller's region index of each
     std::string var_text;                     // their clipped sequences, back to back
     int64_t var_stats[4] = {0, 0, 0, 0};      // pairs kept, entries, tied at a cut, text bytes fetched
@@ -416,37 +417,134 @@ __global__ __launch_bounds__(256) void k_a2c_bin_fill(A2CBinArgs A)
     }
 }
 
-struct A2CInsArgs {
+// ---- the distinct strings of the (class, row) pairs of one call ------------
+// Pair p = cls * n_rows + row.  A hash kernel of the caller writes h[p], the
+// key of the pair's string (0: the pair produces none), and counts the keyed
+// pairs in ctr[0]; an open-addressing table of at least twice that many
+// slots then holds per key the summed count of its rows and the first of
+// them (k_a2c_tab_count); a verify kernel of the caller compares every pair
+// with its slot's first row (ctr[1]: pairs that differ, an error of the
+// call); the occupied slots leave as entries (k_a2c_tab_compact, ctr[2]).
+struct A2CTable {
+    const A2CRow *rows;      // the rows of the call: its group's, or a rank's part of them
+    int64_t n_rows, n_pairs;
+    uint64_t *h;
+    uint64_t *tkey;          // 0 = free
+    unsigned long long *tcnt;
+    uint32_t *tfirst;        // index in rows
+    int32_t *tclass;
+    uint64_t mask;
+    A2CDistinct *entries;
+    unsigned long long *ctr;
+};
+
+__device__ __forceinline__ uint64_t a2c_slot(uint64_t h, uint64_t mask)
+{
+    return ((h * 0x9e3779b97f4a7c15ull) >> 20) & mask;
+}
+
+__device__ __forceinline__ unsigned long long a2c_wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+__device__ void a2c_table_add(const A2CTable &T, uint64_t h, int cls, unsigned long long cnt, uint32_t first)
+{
+    const TableSlot c = table_claim(T.tkey, T.mask, a2c_slot(h, T.mask), h);
+    if (c.created) T.tclass[c.slot] = cls;
+    atomicAdd(&T.tcnt[c.slot], cnt);
+    atomicMin(&T.tfirst[c.slot], first);
+}
+
+constexpr int A2C_COMBINE = 4;           // rounds of equal-key combining in a wave
+
+// A thread per pair.  Equal keys of a wave are combined first (the dominant
+// string is most of every wave, and atomics on one address serialise): for
+// A2C_COMBINE rounds the lanes holding the lowest active lane's key add their
+// counts up and take their least row, and that lane alone goes to the table;
+// what is left goes lane by lane.
+__global__ __launch_bounds__(256) void k_a2c_tab_count(A2CTable T)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t h = 0;
+    uint32_t idx = 0;
+    unsigned long long cnt = 0;
+    int cls = 0;
+    if (p < T.n_pairs) {
+        h = T.h[p];
+        idx = (uint32_t)(p % T.n_rows);
+        cls = (int)(p / T.n_rows);
+        if (h) cnt = T.rows[idx].cnt;
+    }
+    bool todo = h != 0;
+    for (int round = 0; round < A2C_COMBINE; ++round) {
+        const unsigned long long act = __ballot(todo);
+        if (!act) break;
+        const int leader = __ffsll((long long)act) - 1;
+        const uint64_t k = __shfl((unsigned long long)h, leader);
+        const bool mine = todo && h == k;
+        const unsigned long long sum = a2c_wave_sum(mine ? cnt : 0ull);
+        uint32_t mn = mine ? idx : A2C_NONE;
+#pragma unroll
+        for (int d = 32; d; d >>= 1) {
+            const uint32_t o = __shfl_xor(mn, d);
+            mn = o < mn ? o : mn;
+        }
+        if (lane == leader) a2c_table_add(T, h, cls, sum, mn);
+        todo = todo && !mine;
+    }
+    if (todo) a2c_table_add(T, h, cls, cnt, idx);
+}
+
+// The occupied slots as entries, one counter atomic per wave.  Args derives
+// from A2CTable and gives a2c_entry_len(A, cls, first): the entry's len.
+template <class Args>
+__global__ __launch_bounds__(256) void k_a2c_tab_compact(Args A)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool used = s <= A.mask && A.tkey[s] != 0;
+    const unsigned long long b = __ballot(used);
+    if (!b) return;
+    unsigned long long base = 0;
+    const int leader = __ffsll((long long)b) - 1;
+    if (lane == leader) base = atomicAdd(&A.ctr[2], (unsigned long long)__popcll(b));
+    base = __shfl(base, leader);
+    if (!used) return;
+    A2CDistinct e;
+    e.cls = A.tclass[s];
+    e.first = A.tfirst[s];
+    e.count = A.tcnt[s];
+    e.pad = 0;
+    e.len = a2c_entry_len(A, e.cls, e.first);
+    A.entries[base + __popcll(b & ((1ull << lane) - 1))] = e;
+}
+
+struct A2CInsArgs : A2CTable {
     const uint8_t *text;
-    const A2CRow *rows;      // the rows of one group
-    uint32_t row0;           // rows[0].local: a first-row number minus row0 indexes rows
-                             // (a rank's part of a group starts at the ranks before's rows)
     const int8_t *code;
     const uint8_t *cls;
     const int32_t *left, *right;
-    int64_t n_rows, n_pairs;
     int frame;
-    uint64_t *h;             // per (range, row): 0 = no insertion string
-    uint64_t *tkey;
-    unsigned long long *tcnt;
-    uint32_t *tfirst;
-    int32_t *trange;
-    uint64_t mask;
-    A2CEntry *entries;
-    unsigned long long *ctr; // [0] strings, [1] collisions, [2] entries
 };
 
 // The framed slice of one read for one range (:787-791): read indices
 // [lo, lo + 3 n) of its whole codons, or false when the slice starts in the
 // '-' padding, is empty, holds '-' or 'n', or translates to nothing.
-__device__ bool a2c_slice(const A2CInsArgs &A, const A2CRow &R, int rg, int &lo, int &n)
+// scan = false gives the indices without reading the bytes: only for a row
+// that k_a2c_ins_hash already keyed for this range (an entry's first row),
+// which therefore passed the scan.
+__device__ bool a2c_slice(const A2CInsArgs &A, const A2CRow &R, int rg, int &lo, int &n, bool scan = true)
 {
     const int64_t s = 3LL * A.left[rg] - A.frame - R.off;
     int64_t e = 3LL * A.right[rg] - A.frame - R.off;
     if (e > R.len) e = R.len;
     if (s < 0 || e - s < 3) return false;
     const uint8_t *p = A.text + R.soff;
-    for (int64_t q = s; q < e; ++q) {
+    for (int64_t q = s; scan && q < e; ++q) {
         const uint8_t c = A.cls[p[q]];
         if (c == A2C_DASH || c == A2C_GAP) return false;
     }
@@ -468,11 +566,12 @@ __device__ __forceinline__ uint64_t a2c_mix(uint64_t z)
     return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ int64_t a2c_find(const A2CInsArgs &A, uint64_t h)
+// the codons of an entry's string (k_a2c_tab_compact)
+__device__ __forceinline__ int a2c_entry_len(const A2CInsArgs &A, int rg, uint32_t first)
 {
-    uint64_t s = (h >> 7) & A.mask;
-    while (A.tkey[s] != h) s = (s + 1) & A.mask;
-    return (int64_t)s;
+    int lo = 0, n = 0;
+    a2c_slice(A, A.rows[first], rg, lo, n, false);
+    return n;
 }
 
 __global__ __launch_bounds__(256) void k_a2c_ins_hash(A2CInsArgs A)
@@ -497,27 +596,6 @@ __global__ __launch_bounds__(256) void k_a2c_ins_hash(A2CInsArgs A)
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&A.ctr[0], (unsigned long long)__popcll(b));
 }
 
-__global__ __launch_bounds__(256) void k_a2c_ins_count(A2CInsArgs A)
-{
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= A.n_pairs) return;
-    const uint64_t h = A.h[p];
-    if (!h) return;
-    const A2CRow R = A.rows[p % A.n_rows];
-    uint64_t s = (h >> 7) & A.mask;
-    for (;;) {
-        const unsigned long long old =
-            atomicCAS((unsigned long long *)&A.tkey[s], 0ull, (unsigned long long)h);
-        if (old == 0ull || old == h) {
-            if (old == 0ull) A.trange[s] = (int32_t)(p / A.n_rows);
-            atomicAdd(&A.tcnt[s], (unsigned long long)R.cnt);
-            atomicMin(&A.tfirst[s], R.local);
-            return;
-        }
-        s = (s + 1) & A.mask;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_a2c_ins_verify(A2CInsArgs A)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -525,10 +603,10 @@ __global__ __launch_bounds__(256) void k_a2c_ins_verify(A2CInsArgs A)
     const uint64_t h = A.h[p];
     if (!h) return;
     const int rg = (int)(p / A.n_rows);
-    const int64_t s = a2c_find(A, h);
-    const A2CRow R = A.rows[p % A.n_rows], F = A.rows[A.tfirst[s] - A.row0];
+    const uint64_t s = table_find(A.tkey, A.mask, a2c_slot(h, A.mask), h);
+    const A2CRow R = A.rows[p % A.n_rows], F = A.rows[A.tfirst[s]];
     int lo = 0, n = 0, flo = 0, fn = 0;
-    bool same = A.trange[s] == rg && a2c_slice(A, R, rg, lo, n) && a2c_slice(A, F, rg, flo, fn) &&
+    bool same = A.tclass[s] == rg && a2c_slice(A, R, rg, lo, n) && a2c_slice(A, F, rg, flo, fn) &&
                 n == fn;
     const uint8_t *pr = A.text + R.soff, *pf = A.text + F.soff;
     for (int k = 0; same && k < n; ++k)
@@ -536,33 +614,21 @@ __global__ __launch_bounds__(256) void k_a2c_ins_verify(A2CInsArgs A)
     if (!same) atomicAdd(&A.ctr[1], 1ull);
 }
 
-__global__ __launch_bounds__(256) void k_a2c_ins_compact(A2CInsArgs A)
-{
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s > A.mask || !A.tkey[s]) return;
-    A2CEntry e;
-    e.range = A.trange[s];
-    e.first = A.tfirst[s];
-    e.count = A.tcnt[s];
-    int lo = 0, n = 0;
-    a2c_slice(A, A.rows[e.first - A.row0], e.range, lo, n);
-    e.lo = lo;
-    e.n_codons = n;
-    A.entries[atomicAdd(&A.ctr[2], 1ull)] = e;
-}
-
 // amino-acid strings of the (sorted) entries, each followed by '\n'
-__global__ __launch_bounds__(256) void k_a2c_ins_gather(A2CInsArgs A, const A2CEntry *ent,
+__global__ __launch_bounds__(256) void k_a2c_ins_gather(A2CInsArgs A, const A2CDistinct *ent,
                                                         const int64_t *eoff, int64_t n_ent,
                                                         char *out)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n_ent) return;
-    const A2CEntry e = ent[k];
-    const uint8_t *s = A.text + A.rows[e.first - A.row0].soff;
+    const A2CDistinct e = ent[k];
+    const A2CRow F = A.rows[e.first];
+    const uint8_t *s = A.text + F.soff;
+    int lo = 0, n = 0;
+    a2c_slice(A, F, e.cls, lo, n, false);
     char *o = out + eoff[k];
-    for (int c = 0; c < e.n_codons; ++c) o[c] = c_a2c_codes[a2c_codon(A, s, e.lo + 3 * c)];
-    o[e.n_codons] = '\n';
+    for (int c = 0; c < e.len; ++c) o[c] = c_a2c_codes[a2c_codon(A, s, lo + 3 * c)];
+    o[e.len] = '\n';
 }
 
 // ---------------------------------------------------------------------------
@@ -965,6 +1031,72 @@ static void a2c_clear_inserts(A2CState &S)
     S.var_text.clear();
 }
 
+// The device memory of one call: every allocation is freed when the holder
+// goes, however the call returns (move-only, as its unique_ptrs are).
+struct A2CDevFree {
+    void operator()(void *p) const { hipFree(p); }
+};
+struct A2CDevMem {
+    std::vector<std::unique_ptr<void, A2CDevFree>> held;
+    template <class T> hipError_t alloc(T *&p, size_t n)
+    {
+        p = nullptr;
+        const hipError_t e = hipMalloc(&p, sizeof(T) * n);
+        if (e == hipSuccess) held.emplace_back(p);
+        return e;
+    }
+};
+
+// The middle of mh_a2c_inserts and mh_a2c_variants: a.h is filled and
+// ctr[0] (on the host) counts its keys.  Sizes, allocates and clears the
+// table, groups (k_a2c_tab_count), verifies with the caller's kernel, compacts
+// and reads the counters back: a.entries[0 .. ctr[2]) are on the device in no
+// particular order.  who: the calling function, for a failure's text; label:
+// the profile names of the three launches (a name repeated takes them under
+// one bracket).  -4 with the caller's message when distinct strings share a
+// key.
+template <class Args>
+static int a2c_group_strings(Ctx &c, A2CDevMem &mem, Args &a, unsigned long long *ctr,
+                             void (*verify)(Args), unsigned verify_blocks, const char *who,
+                             const char *const label[3], const char *collision)
+{
+    hipStream_t s = c.stream;
+    uint64_t tsize = 1024;
+    while (tsize < 2 * ctr[0]) tsize <<= 1;
+    hipError_t e = mem.alloc(a.tkey, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tcnt, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tfirst, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tclass, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.entries, ctr[0]);
+    if (e == hipSuccess) e = hipMemsetAsync(a.tkey, 0, sizeof(uint64_t) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.tcnt, 0, sizeof(unsigned long long) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.tfirst, 0xff, sizeof(uint32_t) * tsize, s);
+    if (e != hipSuccess) return hip_fail(e, (std::string(who) + " table").c_str());
+    a.mask = tsize - 1;
+    const dim3 pair_blocks((unsigned)((a.n_pairs + 255) / 256)), slot_blocks((unsigned)((tsize + 255) / 256));
+    int p = prof_begin(c, label[0]);
+    auto next = [&](int k) {
+        if (strcmp(label[k], label[k - 1]) == 0) return;
+        prof_end(c, p);
+        p = prof_begin(c, label[k]);
+    };
+    hipLaunchKernelGGL(k_a2c_tab_count, pair_blocks, dim3(256), 0, s, static_cast<const A2CTable &>(a));
+    next(1);
+    hipLaunchKernelGGL(verify, dim3(verify_blocks), dim3(256), 0, s, a);
+    next(2);
+    hipLaunchKernelGGL(k_a2c_tab_compact<Args>, slot_blocks, dim3(256), 0, s, a);
+    prof_end(c, p);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, a.ctr, 3 * sizeof(*ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, label[0]);
+    if (ctr[1]) {
+        set_error("%s", collision);
+        return -4;
+    }
+    return 0;
+}
+
 }  // namespace mh
 
 using namespace mh;
@@ -1309,6 +1441,86 @@ extern "C" int mh_a2c_counts(mh_ctx *ctx, int slot, int64_t g, int frame, uint32
     return 0;
 }
 
+// mh_a2c_inserts past its checks: the entries of the group's np > 0 (range,
+// row) pairs and their strings into S
+static int a2c_inserts_run(Ctx &c, A2CState &S, int64_t g, int frame, int n_ranges,
+                           const int32_t *left, const int32_t *right)
+{
+    static const char *const label[3] = {"k_a2c_ins", "k_a2c_ins", "k_a2c_ins"};
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * n_ranges;
+    const unsigned pair_blocks = (unsigned)((np + 255) / 256);
+    hipStream_t s = c.stream;
+    A2CDevMem mem;
+    A2CInsArgs a{};
+    int32_t *d_lr;
+    A2CDistinct *d_sorted;
+    int64_t *d_eoff;
+    char *d_out;
+    unsigned long long ctr[3] = {0, 0, 0};
+    std::vector<int32_t> lr(2 * (size_t)n_ranges);
+    for (int k = 0; k < n_ranges; ++k) { lr[k] = left[k]; lr[n_ranges + k] = right[k]; }
+    hipError_t e = mem.alloc(d_lr, lr.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lr, lr.data(), sizeof(int32_t) * lr.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = mem.alloc(a.h, (size_t)np);
+    if (e == hipSuccess) e = mem.alloc(a.ctr, 3);
+    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, sizeof(ctr), s);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_inserts alloc");
+    a.text = S.d_text;
+    a.rows = S.d_rows + S.g_first[g];
+    a.code = S.d_code;
+    a.cls = S.d_cls;
+    a.left = d_lr;
+    a.right = d_lr + n_ranges;
+    a.n_rows = nr;
+    a.n_pairs = np;
+    a.frame = frame;
+    {
+        const int p0 = prof_begin(c, label[0]);
+        hipLaunchKernelGGL(k_a2c_ins_hash, dim3(pair_blocks), dim3(256), 0, s, a);
+        prof_end(c, p0);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "k_a2c_ins_hash");
+    if (ctr[0] == 0) return 0;
+    if (int rc = a2c_group_strings(c, mem, a, ctr, k_a2c_ins_verify, pair_blocks, "mh_a2c_inserts", label,
+                                   "aln2counts: insertion-string hash collision (distinct strings share a key)"))
+        return rc;
+    std::vector<A2CDistinct> ent(ctr[2]);
+    e = copy_sync(c, ent.data(), a.entries, sizeof(A2CDistinct) * ent.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_inserts fetch");
+    // InsertionWriter order: ranges in order, then Counter insertion order
+    std::sort(ent.begin(), ent.end(), [](const A2CDistinct &x, const A2CDistinct &y) {
+        return x.cls != y.cls ? x.cls < y.cls : x.first < y.first;
+    });
+    std::vector<int64_t> eoff(ent.size() + 1);
+    eoff[0] = 0;
+    for (size_t k = 0; k < ent.size(); ++k) eoff[k + 1] = eoff[k] + ent[k].len + 1;
+    S.aminos.assign((size_t)eoff.back(), '\0');
+    e = mem.alloc(d_sorted, ent.size());
+    if (e == hipSuccess) e = mem.alloc(d_eoff, eoff.size());
+    if (e == hipSuccess) e = mem.alloc(d_out, (size_t)eoff.back());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sorted, ent.data(), sizeof(A2CDistinct) * ent.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * eoff.size(), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_inserts gather");
+    hipLaunchKernelGGL(k_a2c_ins_gather, dim3((unsigned)((ent.size() + 255) / 256)), dim3(256), 0, s,
+                       a, d_sorted, d_eoff, (int64_t)ent.size(), d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&S.aminos[0], d_out, (size_t)eoff.back(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "k_a2c_ins_gather");
+    // first rows leave as row numbers within the whole group.  This relies on
+    // local being contiguous over a call's rows, rows[i].local ==
+    // rows[0].local + i, as a2c_layout and mh_a2c_part_count number them (a
+    // rank's part of a group starts at the rows of the ranks before; rows
+    // built on the device are whole groups, from 0)
+    const uint32_t base = S.dev_rows ? 0 : S.rows[(size_t)S.g_first[g]].local;
+    for (A2CDistinct &x : ent) x.first += base;
+    S.entries = std::move(ent);
+    return 0;
+}
+
 extern "C" int mh_a2c_inserts(mh_ctx *ctx, int slot, int64_t g, int frame, int n_ranges,
                               const int32_t *left, const int32_t *right, int64_t *n_entries)
 {
@@ -1327,122 +1539,13 @@ extern "C" int mh_a2c_inserts(mh_ctx *ctx, int slot, int64_t g, int frame, int n
             set_error("mh_a2c_inserts: bad range %d..%d", left[k], right[k]);
             return -3;
         }
-    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * n_ranges;
-    if (np == 0) return 0;
+    if ((S.g_first[g + 1] - S.g_first[g]) * n_ranges == 0) return 0;
     auto t0 = std::chrono::steady_clock::now();
-    hipStream_t s = c.stream;
-    int32_t *d_lr = nullptr;
-    uint64_t *d_h = nullptr, *d_tkey = nullptr;
-    unsigned long long *d_tcnt = nullptr, *d_ctr = nullptr;
-    uint32_t *d_tfirst = nullptr;
-    int32_t *d_trange = nullptr;
-    A2CEntry *d_ent = nullptr, *d_sorted = nullptr;
-    int64_t *d_eoff = nullptr;
-    char *d_out = nullptr;
-    int rc = 0;
-    auto fail = [&](hipError_t e, const char *what) {
-        rc = hip_fail(e, what);
-        return rc;
-    };
-    A2CInsArgs a{};
-    uint64_t tsize = 1024;
-    unsigned long long ctr[3] = {0, 0, 0};
-    std::vector<int32_t> lr(2 * (size_t)n_ranges);
-    std::vector<A2CEntry> ent;
-    std::vector<int64_t> eoff;
-    hipError_t e = hipMalloc(&d_lr, sizeof(int32_t) * lr.size());
-    for (int k = 0; k < n_ranges; ++k) { lr[k] = left[k]; lr[n_ranges + k] = right[k]; }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lr, lr.data(), sizeof(int32_t) * lr.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMalloc(&d_h, sizeof(uint64_t) * np);
-    if (e == hipSuccess) e = hipMalloc(&d_ctr, sizeof(unsigned long long) * 3);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, sizeof(unsigned long long) * 3, s);
-    if (e != hipSuccess) { fail(e, "mh_a2c_inserts alloc"); goto done; }
-    a.text = S.d_text;
-    a.rows = S.d_rows + S.g_first[g];
-    a.row0 = S.dev_rows ? 0 : S.rows[(size_t)S.g_first[g]].local;
-    a.code = S.d_code;
-    a.cls = S.d_cls;
-    a.left = d_lr;
-    a.right = d_lr + n_ranges;
-    a.n_rows = nr;
-    a.n_pairs = np;
-    a.frame = frame;
-    a.h = d_h;
-    a.ctr = d_ctr;
-    {
-        const int p0 = prof_begin(c, "k_a2c_ins");
-        hipLaunchKernelGGL(k_a2c_ins_hash, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, a);
-        prof_end(c, p0);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { fail(e, "k_a2c_ins_hash"); goto done; }
-    if (ctr[0] == 0) goto done;
-    while (tsize < 2 * ctr[0]) tsize <<= 1;
-    e = hipMalloc(&d_tkey, sizeof(uint64_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_tcnt, sizeof(unsigned long long) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_tfirst, sizeof(uint32_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_trange, sizeof(int32_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_ent, sizeof(A2CEntry) * ctr[0]);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tkey, 0, sizeof(uint64_t) * tsize, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tcnt, 0, sizeof(unsigned long long) * tsize, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tfirst, 0xff, sizeof(uint32_t) * tsize, s);
-    if (e != hipSuccess) { fail(e, "mh_a2c_inserts table"); goto done; }
-    a.tkey = d_tkey;
-    a.tcnt = d_tcnt;
-    a.tfirst = d_tfirst;
-    a.trange = d_trange;
-    a.mask = tsize - 1;
-    a.entries = d_ent;
-    {
-        const int p0 = prof_begin(c, "k_a2c_ins");
-        hipLaunchKernelGGL(k_a2c_ins_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_a2c_ins_verify, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_a2c_ins_compact, dim3((unsigned)((tsize + 255) / 256)), dim3(256), 0, s, a);
-        prof_end(c, p0);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { fail(e, "k_a2c_ins"); goto done; }
-    if (ctr[1]) {
-        set_error("aln2counts: insertion-string hash collision (distinct strings share a key)");
-        rc = -4;
-        goto done;
-    }
-    ent.resize(ctr[2]);
-    e = copy_sync(c, ent.data(), d_ent, sizeof(A2CEntry) * ent.size(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { fail(e, "mh_a2c_inserts fetch"); goto done; }
-    // InsertionWriter order: ranges in order, then Counter insertion order
-    std::sort(ent.begin(), ent.end(), [](const A2CEntry &x, const A2CEntry &y) {
-        return x.range != y.range ? x.range < y.range : x.first < y.first;
-    });
-    eoff.resize(ent.size() + 1);
-    eoff[0] = 0;
-    for (size_t k = 0; k < ent.size(); ++k) eoff[k + 1] = eoff[k] + ent[k].n_codons + 1;
-    S.aminos.assign((size_t)eoff.back(), '\0');
-    e = hipMalloc(&d_sorted, sizeof(A2CEntry) * ent.size());
-    if (e == hipSuccess) e = hipMalloc(&d_eoff, sizeof(int64_t) * eoff.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)eoff.back());
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sorted, ent.data(), sizeof(A2CEntry) * ent.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * eoff.size(), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { fail(e, "mh_a2c_inserts gather"); goto done; }
-    hipLaunchKernelGGL(k_a2c_ins_gather, dim3((unsigned)((ent.size() + 255) / 256)), dim3(256), 0, s,
-                       a, d_sorted, d_eoff, (int64_t)ent.size(), d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&S.aminos[0], d_out, (size_t)eoff.back(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { fail(e, "k_a2c_ins_gather"); goto done; }
-    S.entries = std::move(ent);
-    if (n_entries) *n_entries = (int64_t)S.entries.size();
-done:
-    hipFree(d_lr); hipFree(d_h); hipFree(d_ctr); hipFree(d_tkey); hipFree(d_tcnt);
-    hipFree(d_tfirst); hipFree(d_trange); hipFree(d_ent); hipFree(d_sorted); hipFree(d_eoff);
-    hipFree(d_out);
+    const int rc = a2c_inserts_run(c, S, g, frame, n_ranges, left, right);
     prof_flush(c);
     S.t_ins += ms_since(t0);
     if (rc) a2c_clear_inserts(S);
+    else if (n_entries) *n_entries = (int64_t)S.entries.size();
     return rc;
 }
 
@@ -1453,7 +1556,7 @@ extern "C" int mh_a2c_insert_entries(mh_ctx *ctx, int slot, int32_t *range, int6
     Ctx &c = *ctx_of(ctx);
     A2CState &S = *a2c_state(c, slot);
     for (size_t k = 0; k < S.entries.size(); ++k) {
-        if (range) range[k] = S.entries[k].range;
+        if (range) range[k] = S.entries[k].cls;
         if (count) count[k] = (int64_t)S.entries[k].count;
         if (first) first[k] = S.entries[k].first;
     }
@@ -1490,7 +1593,7 @@ extern "C" int mh_a2c_insert_rows(mh_ctx *ctx, int slot, const char *lead, int n
         for (size_t k = 0; k < S.entries.size(); ++k) {
             const char *nl = (const char *)memchr(am, '\n', (size_t)(am_end - am));
             if (!nl) { set_error("mh_a2c_insert_rows: entry strings out of step"); return -3; }
-            const int r = S.entries[k].range;
+            const int r = S.entries[k].cls;
             if (r < 0 || r >= n_ranges) { set_error("mh_a2c_insert_rows: range %d out of %d", r, n_ranges); return -3; }
             o.append(lead, ll);
             put((long long)left[r] + 1);
@@ -1754,8 +1857,8 @@ extern "C" int mh_a2c_insert_export(mh_ctx *ctx, int slot, uint8_t *buf, size_t 
     if (cap < need) { set_error("mh_a2c_insert_export: buffer too small"); return -2; }
     memset(buf, 0, need);
     for (size_t k = 0; k < S.entries.size(); ++k) {
-        const A2CEntry &e = S.entries[k];
-        A2CWireEntry w{e.range, e.first, e.n_codons, (int32_t)str[k].second, e.count};
+        const A2CDistinct &e = S.entries[k];
+        A2CWireEntry w{e.cls, e.first, e.len, (int32_t)str[k].second, e.count};
         memcpy(buf, &w, sizeof w);
         memcpy(buf + sizeof w, str[k].first, str[k].second);
         buf += sizeof w + ((str[k].second + 7) & ~(size_t)7);
@@ -1771,7 +1874,7 @@ extern "C" int mh_a2c_insert_merge(mh_ctx *ctx, int slot, const uint8_t *buf, in
     if (!ctx || slot < 0 || slot >= A2C_SLOTS || (!buf && len) || len < 0) return -3;
     Ctx &c = *ctx_of(ctx);
     A2CState &S = *a2c_state(c, slot);
-    std::map<std::pair<int32_t, std::string>, A2CEntry> merged;
+    std::map<std::pair<int32_t, std::string>, A2CDistinct> merged;
     int64_t at = 0;
     while (at < len) {
         if (len - at < (int64_t)sizeof(A2CWireEntry)) { set_error("mh_a2c_insert_merge: malformed"); return -3; }
@@ -1782,17 +1885,17 @@ extern "C" int mh_a2c_insert_merge(mh_ctx *ctx, int slot, const uint8_t *buf, in
         std::string key((const char *)buf + at + sizeof w, (size_t)w.slen);
         auto it = merged.find({w.range, key});
         if (it == merged.end()) {
-            merged.emplace(std::make_pair(w.range, std::move(key)), A2CEntry{w.range, w.first, w.n_codons, 0, w.count});
+            merged.emplace(std::make_pair(w.range, std::move(key)), A2CDistinct{w.range, w.first, w.n_codons, 0, w.count});
         } else {
             it->second.count += w.count;
             it->second.first = std::min(it->second.first, w.first);
         }
         at += sz;
     }
-    std::vector<std::pair<const std::string *, A2CEntry>> v;
+    std::vector<std::pair<const std::string *, A2CDistinct>> v;
     for (auto &kv : merged) v.push_back({&kv.first.second, kv.second});
     std::sort(v.begin(), v.end(), [](const auto &x, const auto &y) {
-        return x.second.range != y.second.range ? x.second.range < y.second.range
+        return x.second.cls != y.second.cls ? x.second.cls < y.second.cls
                                                 : x.second.first < y.second.first;
     });
     S.entries.clear();
@@ -1821,14 +1924,13 @@ extern "C" int mh_a2c_insert_merge(mh_ctx *ctx, int slot, const uint8_t *buf, in
 //                      wave adds the sums up; the length and the region go
 //                      into the key.  A pair whose row cannot hold enough
 //                      bytes of the window is rejected before any is read.
-//   k_a2c_var_count    a thread per pair: equal keys of a wave are combined
-//                      (the dominant variant is most of every wave) before one
-//                      lane claims / finds the slot and adds count and first
-//                      row, as k_a2c_ins_count does per thread.
+//   k_a2c_tab_count    (shared with the insertion strings, profiled here as
+//                      k_a2c_var_count) the keys grouped: count and first row.
 //   k_a2c_var_verify   a wavefront per pair: its window against the window
 //                      of its entry's first row, byte for byte; a mismatch is
 //                      an error of the call, never a merged count.
-//   k_a2c_var_compact  the occupied slots as entries.
+//   k_a2c_tab_compact  (shared, profiled as k_a2c_var_compact) the occupied
+//                      slots as entries.
 //   k_a2c_var_select   a block per (slice of entries, region), max_variants
 //                      rounds: the largest count among the entries not kept
 //                      yet, then among the entries tied at it the greatest
@@ -1845,23 +1947,12 @@ extern "C" int mh_a2c_insert_merge(mh_ctx *ctx, int slot, const uint8_t *buf, in
 // ---------------------------------------------------------------------------
 namespace mh {
 
-constexpr int A2C_VAR_COMBINE = 4;       // rounds of equal-key combining in a wave
 constexpr int A2C_VAR_SLICE = 2048;      // entries a block of the first selection level takes
 
-struct A2CVarArgs {
+struct A2CVarArgs : A2CTable {
     const uint8_t *text;
-    const A2CRow *rows;          // the rows of one group
     const int64_t *win;          // per region: start, end, reference length, max_variants
-    int64_t n_rows, n_pairs;
     int key_bits;
-    uint64_t *h;                 // per (region, row): 0 = does not count
-    uint64_t *tkey;
-    unsigned long long *tcnt;
-    uint32_t *tfirst;
-    int32_t *tregion;
-    uint64_t mask;
-    A2CVarEntry *entries;
-    unsigned long long *ctr;     // [0] pairs that count, [1] mismatches, [2] entries
 };
 
 // clipped = ('-' * off + seq)[start:end]: padded positions [lo, hi)
@@ -1878,18 +1969,6 @@ __device__ __forceinline__ void a2c_var_clip(const A2CRow &R, int64_t start, int
 __device__ __forceinline__ uint32_t a2c_var_byte(const uint8_t *text, const A2CRow &R, int64_t pos)
 {
     return pos < R.off ? (uint32_t)'-' : (uint32_t)text[R.soff + (pos - R.off)];
-}
-
-__device__ __forceinline__ uint64_t a2c_var_slot(uint64_t h, uint64_t mask)
-{
-    return ((h * 0x9e3779b97f4a7c15ull) >> 20) & mask;
-}
-
-__device__ __forceinline__ unsigned long long a2c_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void k_a2c_var_hash(A2CVarArgs A)
@@ -1927,56 +2006,6 @@ __global__ __launch_bounds__(256) void k_a2c_var_hash(A2CVarArgs A)
     if (lane == 0 && kept) atomicAdd(&A.ctr[0], kept);
 }
 
-__device__ void a2c_var_add(const A2CVarArgs &A, uint64_t h, int rg, unsigned long long cnt, uint32_t first)
-{
-    uint64_t s = a2c_var_slot(h, A.mask);
-    for (;;) {
-        const unsigned long long old =
-            atomicCAS((unsigned long long *)&A.tkey[s], 0ull, (unsigned long long)h);
-        if (old == 0ull || old == h) {
-            if (old == 0ull) A.tregion[s] = rg;
-            atomicAdd(&A.tcnt[s], cnt);
-            atomicMin(&A.tfirst[s], first);
-            return;
-        }
-        s = (s + 1) & A.mask;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_a2c_var_count(A2CVarArgs A)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    uint64_t h = 0;
-    uint32_t idx = 0;
-    unsigned long long cnt = 0;
-    int rg = 0;
-    if (p < A.n_pairs) {
-        h = A.h[p];
-        idx = (uint32_t)(p % A.n_rows);
-        rg = (int)(p / A.n_rows);
-        if (h) cnt = A.rows[idx].cnt;
-    }
-    bool todo = h != 0;
-    for (int round = 0; round < A2C_VAR_COMBINE; ++round) {
-        const unsigned long long act = __ballot(todo);
-        if (!act) break;
-        const int leader = __ffsll((long long)act) - 1;
-        const uint64_t k = __shfl((unsigned long long)h, leader);
-        const bool mine = todo && h == k;
-        const unsigned long long sum = a2c_wave_sum(mine ? cnt : 0ull);
-        uint32_t mn = mine ? idx : A2C_NONE;
-#pragma unroll
-        for (int d = 32; d; d >>= 1) {
-            const uint32_t o = __shfl_xor(mn, d);
-            mn = o < mn ? o : mn;
-        }
-        if (lane == leader) a2c_var_add(A, h, rg, sum, mn);
-        todo = todo && !mine;
-    }
-    if (todo) a2c_var_add(A, h, rg, cnt, idx);
-}
-
 __global__ __launch_bounds__(256) void k_a2c_var_verify(A2CVarArgs A)
 {
     const int lane = threadIdx.x & 63;
@@ -1987,10 +2016,9 @@ __global__ __launch_bounds__(256) void k_a2c_var_verify(A2CVarArgs A)
         if (!h) continue;
         const int rg = (int)(p / A.n_rows);
         const uint32_t idx = (uint32_t)(p % A.n_rows);
-        uint64_t s = a2c_var_slot(h, A.mask);
-        while (A.tkey[s] != h) s = (s + 1) & A.mask;
+        const uint64_t s = table_find(A.tkey, A.mask, a2c_slot(h, A.mask), h);
         const uint32_t fidx = A.tfirst[s];
-        bool bad = A.tregion[s] != rg;
+        bool bad = A.tclass[s] != rg;
         if (!bad && fidx != idx) {
             const A2CRow R = A.rows[idx], F = A.rows[fidx];
             const int64_t *w = A.win + 4 * rg;
@@ -2007,35 +2035,20 @@ __global__ __launch_bounds__(256) void k_a2c_var_verify(A2CVarArgs A)
     if (lane == 0 && wrong) atomicAdd(&A.ctr[1], wrong);
 }
 
-__global__ __launch_bounds__(256) void k_a2c_var_compact(A2CVarArgs A)
+// the bytes of an entry's clipped sequence (k_a2c_tab_compact)
+__device__ __forceinline__ int a2c_entry_len(const A2CVarArgs &A, int rg, uint32_t first)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool used = s <= A.mask && A.tkey[s] != 0;
-    const unsigned long long b = __ballot(used);
-    if (!b) return;
-    unsigned long long base = 0;
-    const int leader = __ffsll((long long)b) - 1;
-    if (lane == leader) base = atomicAdd(&A.ctr[2], (unsigned long long)__popcll(b));
-    base = __shfl(base, leader);
-    if (!used) return;
-    A2CVarEntry e;
-    e.region = A.tregion[s];
-    e.first = A.tfirst[s];
-    e.count = A.tcnt[s];
-    e.pad = 0;
     int64_t lo, hi;
-    a2c_var_clip(A.rows[e.first], A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
-    e.len = (int32_t)(hi - lo);
-    A.entries[base + __popcll(b & ((1ull << lane) - 1))] = e;
+    a2c_var_clip(A.rows[first], A.win[4 * rg], A.win[4 * rg + 1], lo, hi);
+    return (int)(hi - lo);
 }
 
 // bytes [j, j + 8) of an entry's clipped sequence, big-endian, 0 past its end
-__device__ uint64_t a2c_var_chunk(const A2CVarArgs &A, const A2CVarEntry &e, int64_t j)
+__device__ uint64_t a2c_var_chunk(const A2CVarArgs &A, const A2CDistinct &e, int64_t j)
 {
     const A2CRow F = A.rows[e.first];
     int64_t lo, hi;
-    a2c_var_clip(F, A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
+    a2c_var_clip(F, A.win[4 * e.cls], A.win[4 * e.cls + 1], lo, hi);
     uint64_t key = 0;
 #pragma unroll
     for (int b = 0; b < 8; ++b)
@@ -2051,9 +2064,9 @@ __device__ uint64_t a2c_var_chunk(const A2CVarArgs &A, const A2CVarEntry &e, int
 // the slices' picks (gridDim.x 1, the region's segment of seg_stride
 // entries; unused places hold region -1).  state per entry: 0 free, 1 kept,
 // 2 tied at the round's count and still the greatest on every chunk compared.
-__global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2CVarEntry *src, int64_t n_src,
+__global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2CDistinct *src, int64_t n_src,
                                                          int64_t slice, int64_t seg_stride, uint8_t *state,
-                                                         int64_t cap, A2CVarEntry *out, int32_t *n_out,
+                                                         int64_t cap, A2CDistinct *out, int32_t *n_out,
                                                          unsigned long long *last_out)
 {
     __shared__ unsigned long long s_best, s_key;
@@ -2071,7 +2084,7 @@ __global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2C
         unsigned long long best = 0;
         bool has = false;
         for (int64_t e = b0 + tid; e < b1; e += 1024)
-            if (src[e].region == rg && state[e] != 1) {
+            if (src[e].cls == rg && state[e] != 1) {
                 has = true;
                 best = src[e].count > best ? src[e].count : best;
             }
@@ -2084,7 +2097,7 @@ __global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2C
         best = s_best;
         unsigned int n = 0;
         for (int64_t e = b0 + tid; e < b1; e += 1024)
-            if (src[e].region == rg && state[e] != 1) {
+            if (src[e].cls == rg && state[e] != 1) {
                 const bool tied = src[e].count == best;
                 state[e] = tied ? 2 : 0;
                 n += tied;
@@ -2098,7 +2111,7 @@ __global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2C
             __syncthreads();
             unsigned long long top = 0;
             for (int64_t e = b0 + tid; e < b1; e += 1024)
-                if (state[e] == 2 && src[e].region == rg) {
+                if (state[e] == 2 && src[e].cls == rg) {
                     const unsigned long long k = a2c_var_chunk(A, src[e], j);
                     top = k > top ? k : top;
                 }
@@ -2107,7 +2120,7 @@ __global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2C
             top = s_key;
             n = 0;
             for (int64_t e = b0 + tid; e < b1; e += 1024)
-                if (state[e] == 2 && src[e].region == rg) {
+                if (state[e] == 2 && src[e].cls == rg) {
                     if (a2c_var_chunk(A, src[e], j) == top) ++n;
                     else state[e] = 0;
                 }
@@ -2120,11 +2133,11 @@ __global__ __launch_bounds__(1024) void k_a2c_var_select(A2CVarArgs A, const A2C
         if (tid == 0) s_pick = 0xffffffffu;
         __syncthreads();
         for (int64_t e = b0 + tid; e < b1; e += 1024)
-            if (state[e] == 2 && src[e].region == rg) atomicMin(&s_pick, (unsigned int)(e - b0));
+            if (state[e] == 2 && src[e].cls == rg) atomicMin(&s_pick, (unsigned int)(e - b0));
         __syncthreads();
         const int64_t pick = b0 + s_pick;
         for (int64_t e = b0 + tid; e < b1; e += 1024)
-            if (state[e] == 2 && src[e].region == rg) state[e] = e == pick ? 1 : 0;
+            if (state[e] == 2 && src[e].cls == rg) state[e] = e == pick ? 1 : 0;
         if (tid == 0) out[slot * cap + got] = src[pick];
         last = best;
         __syncthreads();
@@ -2145,7 +2158,7 @@ __global__ __launch_bounds__(256) void k_a2c_var_tied(A2CVarArgs A, int64_t n_en
     const int lane = threadIdx.x & 63;
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int rg = -1;
-    if (e < n_ent && A.entries[e].count == last[A.entries[e].region]) rg = A.entries[e].region;
+    if (e < n_ent && A.entries[e].count == last[A.entries[e].cls]) rg = A.entries[e].cls;
     for (;;) {
         const unsigned long long act = __ballot(rg >= 0);
         if (!act) break;
@@ -2158,20 +2171,161 @@ __global__ __launch_bounds__(256) void k_a2c_var_tied(A2CVarArgs A, int64_t n_en
 }
 
 // a wavefront per kept entry: its clipped sequence at out + off[k]
-__global__ __launch_bounds__(256) void k_a2c_var_gather(A2CVarArgs A, const A2CVarEntry *kept,
+__global__ __launch_bounds__(256) void k_a2c_var_gather(A2CVarArgs A, const A2CDistinct *kept,
                                                         const int64_t *off, int64_t n, char *out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= n) return;
-    const A2CVarEntry e = kept[k];
+    const A2CDistinct e = kept[k];
     const A2CRow F = A.rows[e.first];
     int64_t lo, hi;
-    a2c_var_clip(F, A.win[4 * e.region], A.win[4 * e.region + 1], lo, hi);
+    a2c_var_clip(F, A.win[4 * e.cls], A.win[4 * e.cls + 1], lo, hi);
     for (int64_t i = lane; i < e.len; i += 64) out[off[k] + i] = (char)a2c_var_byte(A.text, F, lo + i);
 }
 
 }  // namespace mh
+
+// mh_a2c_variants past its checks: win / which are the na regions with a cut
+// above 0 (four values each; the caller's index of each), np > 0 pairs
+static int a2c_variants_run(Ctx &c, A2CState &S, int64_t g, const std::vector<int64_t> &win,
+                            const std::vector<int32_t> &which, int key_bits, int64_t *n_kept)
+{
+    static const char *const label[3] = {"k_a2c_var_count", "k_a2c_var_verify", "k_a2c_var_compact"};
+    const int na = (int)which.size();
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * na;
+    hipStream_t s = c.stream;
+    A2CDevMem mem;
+    int64_t *d_win, *d_toff;
+    unsigned long long *d_last;
+    int32_t *d_nkept;
+    A2CDistinct *d_kept, *d_cand = nullptr;
+    uint8_t *d_state;
+    char *d_out;
+    A2CVarArgs a{};
+    unsigned long long ctr[3] = {0, 0, 0};
+    std::vector<int64_t> toff;
+    std::vector<unsigned long long> last_eq;    // per region: its last kept count, entries with it
+    int64_t cap2 = 0;                           // places per region in kept
+    std::vector<int32_t> nk((size_t)na, 0);
+    std::vector<A2CDistinct> kept;
+    const unsigned wave_blocks = (unsigned)std::min<int64_t>((np + 3) / 4, 8192);
+    hipError_t e = mem.alloc(d_win, win.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), sizeof(int64_t) * win.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = mem.alloc(a.h, (size_t)np);
+    if (e == hipSuccess) e = mem.alloc(a.ctr, 3);
+    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, sizeof(ctr), s);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_variants alloc");
+    a.text = S.d_text;
+    a.rows = S.d_rows + S.g_first[g];
+    a.win = d_win;
+    a.n_rows = nr;
+    a.n_pairs = np;
+    a.key_bits = key_bits;
+    {
+        const int p0 = prof_begin(c, "k_a2c_var_hash");
+        hipLaunchKernelGGL(k_a2c_var_hash, dim3(wave_blocks), dim3(256), 0, s, a);
+        prof_end(c, p0);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "k_a2c_var_hash");
+    S.var_stats[0] = (int64_t)ctr[0];
+    if (ctr[0] == 0) return 0;
+    if (int rc = a2c_group_strings(c, mem, a, ctr, k_a2c_var_verify, wave_blocks, "mh_a2c_variants", label,
+                                   "aln2counts: variant hash collision (distinct clipped sequences share a key)"))
+        return rc;
+    S.var_stats[1] = (int64_t)ctr[2];
+    // ---- the cut: every slice's greatest entries, then each region's among those ----
+    {
+        const int64_t n_ent = (int64_t)ctr[2];
+        int64_t most = 0;
+        for (int k = 0; k < na; ++k) most = std::max(most, win[4 * (size_t)k + 3]);
+        const int64_t n_slices = (n_ent + A2C_VAR_SLICE - 1) / A2C_VAR_SLICE;
+        const int64_t cap1 = std::min<int64_t>(most, A2C_VAR_SLICE), seg = n_slices * cap1;
+        const int64_t n_cand = n_slices > 1 ? (int64_t)na * seg : 0;
+        cap2 = std::min<int64_t>(most, n_slices > 1 ? seg : n_ent);
+        const size_t slots = (size_t)na * (size_t)std::max<int64_t>(n_slices, 1);
+        e = mem.alloc(d_state, (size_t)(n_ent + n_cand));
+        if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, (size_t)(n_ent + n_cand), s);
+        if (e == hipSuccess) e = mem.alloc(d_kept, (size_t)na * (size_t)cap2);
+        if (e == hipSuccess) e = mem.alloc(d_nkept, 2 * slots);
+        if (e == hipSuccess) e = mem.alloc(d_last, 2 * slots + (size_t)na);
+        if (e == hipSuccess) e = hipMemsetAsync(d_last, 0, sizeof(unsigned long long) * (2 * slots + (size_t)na), s);
+        if (e == hipSuccess && n_cand) e = mem.alloc(d_cand, (size_t)n_cand);
+        if (e == hipSuccess && n_cand) e = hipMemsetAsync(d_cand, 0xff, sizeof(A2CDistinct) * (size_t)n_cand, s);
+        if (e != hipSuccess) return hip_fail(e, "mh_a2c_variants select");
+        // d_nkept / d_last: [0, slots) the regions' results, [slots, 2 slots) the slices'
+        const int p0 = prof_begin(c, "k_a2c_var_select");
+        if (n_slices > 1) {
+            hipLaunchKernelGGL(k_a2c_var_select, dim3((unsigned)n_slices, (unsigned)na), dim3(1024), 0, s, a,
+                               a.entries, n_ent, (int64_t)A2C_VAR_SLICE, (int64_t)0, d_state, cap1, d_cand,
+                               d_nkept + slots, d_last + slots);
+            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, d_cand, n_cand,
+                               seg, seg, d_state + n_ent, cap2, d_kept, d_nkept, d_last);
+        } else {
+            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, a.entries, n_ent,
+                               n_ent, (int64_t)0, d_state, cap2, d_kept, d_nkept, d_last);
+        }
+        prof_end(c, p0);
+        const int p1 = prof_begin(c, "k_a2c_var_tied");
+        hipLaunchKernelGGL(k_a2c_var_tied, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, a, n_ent,
+                           d_last, d_last + 2 * slots);
+        prof_end(c, p1);
+        e = hipGetLastError();
+        kept.resize((size_t)na * (size_t)cap2);
+        last_eq.resize(2 * (size_t)na);
+        if (e == hipSuccess) e = hipMemcpyAsync(nk.data(), d_nkept, sizeof(int32_t) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && !kept.empty())
+            e = hipMemcpyAsync(kept.data(), d_kept, sizeof(A2CDistinct) * kept.size(), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data(), d_last, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data() + na, d_last + 2 * slots, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hip_fail(e, "k_a2c_var_select");
+    }
+    // ---- the kept entries' text: their summed lengths and nothing else ----
+    {
+        std::vector<A2CDistinct> order;
+        for (int k = 0; k < na; ++k) {
+            if (nk[(size_t)k] < 0 || nk[(size_t)k] > cap2) {
+                set_error("mh_a2c_variants: the selection is inconsistent");
+                return -3;
+            }
+            int64_t at_last = 0;
+            for (int32_t i = 0; i < nk[(size_t)k]; ++i) {
+                order.push_back(kept[(size_t)k * (size_t)cap2 + i]);
+                S.var_region.push_back(which[(size_t)k]);
+                at_last += order.back().count == last_eq[(size_t)k];
+            }
+            // a cut inside a tie: entries left out that share the last kept count
+            if (nk[(size_t)k] == win[4 * (size_t)k + 3] && (int64_t)last_eq[(size_t)na + k] > at_last)
+                S.var_stats[2] += (int64_t)last_eq[(size_t)na + k];
+            if (n_kept) n_kept[which[(size_t)k]] = nk[(size_t)k];
+        }
+        toff.assign(order.size() + 1, 0);
+        for (size_t k = 0; k < order.size(); ++k) toff[k + 1] = toff[k] + order[k].len;
+        S.var_text.assign((size_t)toff.back(), '\0');
+        if (toff.back() > 0) {
+            e = mem.alloc(d_toff, toff.size());
+            if (e == hipSuccess) e = mem.alloc(d_out, (size_t)toff.back());
+            if (e == hipSuccess) e = hipMemcpyAsync(d_toff, toff.data(), sizeof(int64_t) * toff.size(), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_kept, order.data(), sizeof(A2CDistinct) * order.size(), hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) return hip_fail(e, "mh_a2c_variants gather");
+            const int p0 = prof_begin(c, "k_a2c_var_gather");
+            hipLaunchKernelGGL(k_a2c_var_gather, dim3((unsigned)((order.size() + 3) / 4)), dim3(256), 0, s,
+                               a, d_kept, d_toff, (int64_t)order.size(), d_out);
+            prof_end(c, p0);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&S.var_text[0], d_out, (size_t)toff.back(), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) return hip_fail(e, "k_a2c_var_gather");
+            S.var_stats[3] = toff.back();
+        }
+        S.var_entries = std::move(order);
+    }
+    return 0;
+}
 
 extern "C" int mh_a2c_variants(mh_ctx *ctx, int slot, int64_t g, int n_regions, const int64_t *start,
                                const int64_t *end, const int64_t *ref_len, const int64_t *max_variants,
@@ -2204,184 +2358,11 @@ extern "C" int mh_a2c_variants(mh_ctx *ctx, int slot, int64_t g, int n_regions, 
         which.push_back(k);
         win.insert(win.end(), {start[k], end[k], ref_len[k], max_variants[k]});
     }
-    const int na = (int)which.size();
-    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * na;
+    const int64_t np = (S.g_first[g + 1] - S.g_first[g]) * (int64_t)which.size();
     if (np == 0) return 0;
     if (np >= (int64_t)1 << 32) { set_error("mh_a2c_variants: more than 2**32 (region, row) pairs"); return -3; }
     auto t0 = std::chrono::steady_clock::now();
-    hipStream_t s = c.stream;
-    int64_t *d_win = nullptr, *d_toff = nullptr;
-    uint64_t *d_h = nullptr, *d_tkey = nullptr;
-    unsigned long long *d_tcnt = nullptr, *d_ctr = nullptr, *d_last = nullptr;
-    uint32_t *d_tfirst = nullptr;
-    int32_t *d_tregion = nullptr, *d_nkept = nullptr;
-    A2CVarEntry *d_ent = nullptr, *d_kept = nullptr, *d_cand = nullptr;
-    uint8_t *d_state = nullptr;
-    char *d_out = nullptr;
-    int rc = 0;
-    A2CVarArgs a{};
-    uint64_t tsize = 1024;
-    unsigned long long ctr[3] = {0, 0, 0};
-    std::vector<int64_t> toff;
-    std::vector<unsigned long long> last_eq;    // per region: its last kept count, entries with it
-    int64_t cap2 = 0;                           // places per region in kept
-    std::vector<int32_t> nk((size_t)na, 0);
-    std::vector<A2CVarEntry> kept;
-    const unsigned wave_blocks = (unsigned)std::min<int64_t>((np + 3) / 4, 8192);
-    hipError_t e = hipMalloc(&d_win, sizeof(int64_t) * win.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), sizeof(int64_t) * win.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMalloc(&d_h, sizeof(uint64_t) * (size_t)np);
-    if (e == hipSuccess) e = hipMalloc(&d_ctr, sizeof(ctr));
-    if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, sizeof(ctr), s);
-    if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants alloc"); goto done; }
-    a.text = S.d_text;
-    a.rows = S.d_rows + S.g_first[g];
-    a.win = d_win;
-    a.n_rows = nr;
-    a.n_pairs = np;
-    a.key_bits = key_bits;
-    a.h = d_h;
-    a.ctr = d_ctr;
-    {
-        const int p0 = prof_begin(c, "k_a2c_var_hash");
-        hipLaunchKernelGGL(k_a2c_var_hash, dim3(wave_blocks), dim3(256), 0, s, a);
-        prof_end(c, p0);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_hash"); goto done; }
-    S.var_stats[0] = (int64_t)ctr[0];
-    if (ctr[0] == 0) goto done;
-    while (tsize < 2 * ctr[0]) tsize <<= 1;
-    e = hipMalloc(&d_tkey, sizeof(uint64_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_tcnt, sizeof(unsigned long long) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_tfirst, sizeof(uint32_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_tregion, sizeof(int32_t) * tsize);
-    if (e == hipSuccess) e = hipMalloc(&d_ent, sizeof(A2CVarEntry) * ctr[0]);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tkey, 0, sizeof(uint64_t) * tsize, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tcnt, 0, sizeof(unsigned long long) * tsize, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tfirst, 0xff, sizeof(uint32_t) * tsize, s);
-    if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants table"); goto done; }
-    a.tkey = d_tkey;
-    a.tcnt = d_tcnt;
-    a.tfirst = d_tfirst;
-    a.tregion = d_tregion;
-    a.mask = tsize - 1;
-    a.entries = d_ent;
-    {
-        const int p0 = prof_begin(c, "k_a2c_var_count");
-        hipLaunchKernelGGL(k_a2c_var_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, a);
-        prof_end(c, p0);
-        const int p1 = prof_begin(c, "k_a2c_var_verify");
-        hipLaunchKernelGGL(k_a2c_var_verify, dim3(wave_blocks), dim3(256), 0, s, a);
-        prof_end(c, p1);
-        const int p2 = prof_begin(c, "k_a2c_var_compact");
-        hipLaunchKernelGGL(k_a2c_var_compact, dim3((unsigned)((tsize + 255) / 256)), dim3(256), 0, s, a);
-        prof_end(c, p2);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_count"); goto done; }
-    if (ctr[1]) {
-        set_error("aln2counts: variant hash collision (distinct clipped sequences share a key)");
-        rc = -4;
-        goto done;
-    }
-    S.var_stats[1] = (int64_t)ctr[2];
-    // ---- the cut: every slice's greatest entries, then each region's among those ----
-    {
-        const int64_t n_ent = (int64_t)ctr[2];
-        int64_t most = 0;
-        for (int k = 0; k < na; ++k) most = std::max(most, win[4 * (size_t)k + 3]);
-        const int64_t n_slices = (n_ent + A2C_VAR_SLICE - 1) / A2C_VAR_SLICE;
-        const int64_t cap1 = std::min<int64_t>(most, A2C_VAR_SLICE), seg = n_slices * cap1;
-        const int64_t n_cand = n_slices > 1 ? (int64_t)na * seg : 0;
-        cap2 = std::min<int64_t>(most, n_slices > 1 ? seg : n_ent);
-        const size_t slots = (size_t)na * (size_t)std::max<int64_t>(n_slices, 1);
-        e = hipMalloc(&d_state, (size_t)(n_ent + n_cand));
-        if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, (size_t)(n_ent + n_cand), s);
-        if (e == hipSuccess) e = hipMalloc(&d_kept, sizeof(A2CVarEntry) * (size_t)na * (size_t)cap2);
-        if (e == hipSuccess) e = hipMalloc(&d_nkept, sizeof(int32_t) * 2 * slots);
-        if (e == hipSuccess) e = hipMalloc(&d_last, sizeof(unsigned long long) * (2 * slots + (size_t)na));
-        if (e == hipSuccess) e = hipMemsetAsync(d_last, 0, sizeof(unsigned long long) * (2 * slots + (size_t)na), s);
-        if (e == hipSuccess && n_cand) e = hipMalloc(&d_cand, sizeof(A2CVarEntry) * (size_t)n_cand);
-        if (e == hipSuccess && n_cand) e = hipMemsetAsync(d_cand, 0xff, sizeof(A2CVarEntry) * (size_t)n_cand, s);
-        if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants select"); goto done; }
-        // d_nkept / d_last: [0, slots) the regions' results, [slots, 2 slots) the slices'
-        const int p0 = prof_begin(c, "k_a2c_var_select");
-        if (n_slices > 1) {
-            hipLaunchKernelGGL(k_a2c_var_select, dim3((unsigned)n_slices, (unsigned)na), dim3(1024), 0, s, a,
-                               d_ent, n_ent, (int64_t)A2C_VAR_SLICE, (int64_t)0, d_state, cap1, d_cand,
-                               d_nkept + slots, d_last + slots);
-            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, d_cand, n_cand,
-                               seg, seg, d_state + n_ent, cap2, d_kept, d_nkept, d_last);
-        } else {
-            hipLaunchKernelGGL(k_a2c_var_select, dim3(1, (unsigned)na), dim3(1024), 0, s, a, d_ent, n_ent,
-                               n_ent, (int64_t)0, d_state, cap2, d_kept, d_nkept, d_last);
-        }
-        prof_end(c, p0);
-        const int p1 = prof_begin(c, "k_a2c_var_tied");
-        hipLaunchKernelGGL(k_a2c_var_tied, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, a, n_ent,
-                           d_last, d_last + 2 * slots);
-        prof_end(c, p1);
-        e = hipGetLastError();
-        kept.resize((size_t)na * (size_t)cap2);
-        last_eq.resize(2 * (size_t)na);
-        if (e == hipSuccess) e = hipMemcpyAsync(nk.data(), d_nkept, sizeof(int32_t) * (size_t)na, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !kept.empty())
-            e = hipMemcpyAsync(kept.data(), d_kept, sizeof(A2CVarEntry) * kept.size(), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data(), d_last, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(last_eq.data() + na, d_last + 2 * slots, sizeof(unsigned long long) * (size_t)na, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_select"); goto done; }
-    }
-    // ---- the kept entries' text: their summed lengths and nothing else ----
-    {
-        std::vector<A2CVarEntry> order;
-        for (int k = 0; k < na; ++k) {
-            if (nk[(size_t)k] < 0 || nk[(size_t)k] > cap2) {
-                set_error("mh_a2c_variants: the selection is inconsistent");
-                rc = -3;
-                goto done;
-            }
-            int64_t at_last = 0;
-            for (int32_t i = 0; i < nk[(size_t)k]; ++i) {
-                order.push_back(kept[(size_t)k * (size_t)cap2 + i]);
-                S.var_region.push_back(which[(size_t)k]);
-                at_last += order.back().count == last_eq[(size_t)k];
-            }
-            // a cut inside a tie: entries left out that share the last kept count
-            if (nk[(size_t)k] == win[4 * (size_t)k + 3] && (int64_t)last_eq[(size_t)na + k] > at_last)
-                S.var_stats[2] += (int64_t)last_eq[(size_t)na + k];
-            if (n_kept) n_kept[which[(size_t)k]] = nk[(size_t)k];
-        }
-        toff.assign(order.size() + 1, 0);
-        for (size_t k = 0; k < order.size(); ++k) toff[k + 1] = toff[k] + order[k].len;
-        S.var_text.assign((size_t)toff.back(), '\0');
-        if (toff.back() > 0) {
-            e = hipMalloc(&d_toff, sizeof(int64_t) * toff.size());
-            if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)toff.back());
-            if (e == hipSuccess) e = hipMemcpyAsync(d_toff, toff.data(), sizeof(int64_t) * toff.size(), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_kept, order.data(), sizeof(A2CVarEntry) * order.size(), hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) { rc = hip_fail(e, "mh_a2c_variants gather"); goto done; }
-            const int p0 = prof_begin(c, "k_a2c_var_gather");
-            hipLaunchKernelGGL(k_a2c_var_gather, dim3((unsigned)((order.size() + 3) / 4)), dim3(256), 0, s,
-                               a, d_kept, d_toff, (int64_t)order.size(), d_out);
-            prof_end(c, p0);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&S.var_text[0], d_out, (size_t)toff.back(), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { rc = hip_fail(e, "k_a2c_var_gather"); goto done; }
-            S.var_stats[3] = toff.back();
-        }
-        S.var_entries = std::move(order);
-    }
-done:
-    hipFree(d_win); hipFree(d_last); hipFree(d_cand); hipFree(d_toff); hipFree(d_h); hipFree(d_tkey); hipFree(d_tcnt);
-    hipFree(d_ctr); hipFree(d_tfirst); hipFree(d_tregion); hipFree(d_nkept); hipFree(d_ent);
-    hipFree(d_kept); hipFree(d_state); hipFree(d_out);
+    const int rc = a2c_variants_run(c, S, g, win, which, key_bits, n_kept);
     prof_flush(c);
     S.t_var = ms_since(t0);
     if (rc) {

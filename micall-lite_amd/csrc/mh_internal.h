@@ -91,6 +91,34 @@ __host__ __device__ inline uint64_t hash_key(uint64_t k)
     return k;
 }
 
+// Linear probing over a power-of-two table of 64-bit keys cleared to 0 (no
+// key is 0), shared by the grouping tables of sam2aln and aln2counts.
+// table_claim: the slot of `key`, taken with one atomicCAS when no thread
+// has claimed it yet (created: this caller took it).  table_find: the slot
+// of a key that was claimed before the launch.
+struct TableSlot {
+    uint64_t slot;
+    bool created;
+};
+
+__device__ __forceinline__ TableSlot table_claim(uint64_t *tkey, uint64_t mask, uint64_t start,
+                                                 uint64_t key)
+{
+    for (uint64_t s = start;; s = (s + 1) & mask) {
+        const unsigned long long old =
+            atomicCAS((unsigned long long *)&tkey[s], 0ull, (unsigned long long)key);
+        if (old == 0ull || old == key) return {s, old == 0ull};
+    }
+}
+
+__device__ __forceinline__ uint64_t table_find(const uint64_t *tkey, uint64_t mask, uint64_t start,
+                                               uint64_t key)
+{
+    uint64_t s = start;
+    while (tkey[s] != key) s = (s + 1) & mask;
+    return s;
+}
+
 struct Cand {
     int32_t strand, ref, center, support;
 };

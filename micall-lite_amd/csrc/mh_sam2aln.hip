@@ -397,17 +397,9 @@ __global__ __launch_bounds__(256) void k_s2a_count(const int32_t *res, const uin
          u += (int64_t)gridDim.x * blockDim.x) {
         if (res[4 * u] != S2A_OK) continue;
         const uint64_t key = s2a_key(h[2 * u]);
-        uint64_t s = key & mask;
-        for (;;) {
-            const unsigned long long old = atomicCAS((unsigned long long *)&tkey[s], 0ull,
-                                                     (unsigned long long)key);
-            if (old == 0ull || old == key) {
-                atomicAdd(&tcnt[s], 1);
-                atomicMin(&trep[s], (int32_t)u);
-                break;
-            }
-            s = (s + 1) & mask;
-        }
+        const uint64_t s = table_claim(tkey, mask, key & mask, key).slot;
+        atomicAdd(&tcnt[s], 1);
+        atomicMin(&trep[s], (int32_t)u);
     }
 }
 
@@ -423,9 +415,7 @@ __global__ __launch_bounds__(256) void k_s2a_verify(const int32_t *res, const ui
          u += (int64_t)gridDim.x * wpb) {
         if (res[4 * u] != S2A_OK) continue;
         const uint64_t key = s2a_key(h[2 * u]);
-        uint64_t s = key & mask;
-        while (tkey[s] != key) s = (s + 1) & mask;
-        const int64_t r = trep[s];
+        const int64_t r = trep[table_find(tkey, mask, key & mask, key)];
         if (r == u) continue;
         // same group: same rname and same cutoff (entry = unit * n_cut + k)
         bool bad = h[2 * r + 1] != h[2 * u + 1] || uref[r / n_cut] != uref[u / n_cut] ||

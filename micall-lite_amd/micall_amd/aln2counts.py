@@ -12,9 +12,11 @@ byte-identical to the reference's (tests/test_gpu_aln2counts.py).
 Split of the work:
   device -- everything per read: 3-frame codon / base counting of a run,
             with the first row that touched each counter (k_a2c_count), and
-            the grouping of inserted amino-acid strings (k_a2c_ins_*),
-            csrc/mh_a2c.hip.  The first row replaces the reference's Counter
-            insertion order, which decides most_common() ties.
+            the grouping of inserted amino-acid strings (k_a2c_ins_hash /
+            _verify / _gather around k_a2c_tab_count / _compact, the table the
+            nucleotide variants share), csrc/mh_a2c.hip.  The first row
+            replaces the reference's Counter insertion order, which decides
+            most_common() ties.
   host   -- everything per run and O(reference length): consensus letters
             from the counters (numpy), the coordinate mapping with its local
             EmpHIV25 Gotoh alignments (run on the device by mh_gotoh_align)
