@@ -496,6 +496,26 @@ int mh_sam2aln_resident_rows(mh_ctx *ctx, int64_t first, int64_t n, int32_t *len
  * Not sized before (no mh_sam2aln_output size query), it is formatted and
  * written in one pass, the writes overlapping the formatting. */
 int mh_sam2aln_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *written);
+/* clipping.csv of the last sam2aln call on this context (mh_sam2aln_csv_q,
+ * mh_sam2aln_file_q, mh_sam2aln_resident or mh_sam2aln_part): per reference
+ * and 1-based position the number of merged units that soft-clip the
+ * position while no mate aligns it (refname,pos,count; names sorted as
+ * strings, then positions; '\n' line ends; positions may be <= 0 or past
+ * the reference's end).  A unit counts when it reaches the merge (its cause
+ * is none of unmatched, badCigar, 2refs), once whatever the q-cutoffs.
+ * Nothing is computed before the first of these three calls asks: the pass
+ * (k_s2a_clip, k_s2a_clip_scan) then runs over the rows and units the call
+ * left on the device, so ask before the next sam2aln or mapping call.
+ * buf NULL: only *used = bytes needed.  -3 with a message when a
+ * reference's rows span more than 2^26 positions. */
+int mh_sam2aln_clipping(mh_ctx *ctx, char *buf, size_t cap, size_t *used);
+/* The same text written to fd at offset with pwrite; *written = its size. */
+int mh_sam2aln_clipping_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written);
+/* The same counts as arrays in the text's row order: name_id indexes the
+ * call's reference names in first-seen order over its units (the order
+ * mh_sam2aln_part_names prints).  *n = rows; arrays NULL: only *n. */
+int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *count, int64_t cap,
+                           int64_t *n);
 /* What the last mh_sam2aln_write of aligned.csv (which 0, the only one kept)
  * wrote: the crc32 of its text, joined from the formatted pieces' own
  * (nothing is read back), and its size.  -3 when this context's sam2aln

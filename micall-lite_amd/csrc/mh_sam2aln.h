@@ -36,6 +36,35 @@ struct S2AOrder {
     std::vector<int32_t> rows;             // per row: k of uniq[2k], uniq[2k + 1]
 };
 
+// The row arrays the device half reads.  dev: they are on the device already
+// (k_s2a_stage wrote them) and span[r] is row r's reference span; without it
+// they are uploaded from S and the spans come from S.cig
+struct S2ADevRows {
+    const uint8_t *seq, *qual;
+    const int64_t *soff;
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int32_t *span;                // host: S2AState::d_spanins per row
+};
+
+// soft-clip counts of the last call (mh_sam2aln_clipping), counted on the
+// first request from the rows and units the merge left on the device
+enum { CLIP_NONE = 0, CLIP_ROWS = 1, CLIP_DONE = 2 };
+constexpr int64_t S2A_CLIP_MAX_WINDOW = (int64_t)1 << 26;   // positions of one reference
+
+struct S2AClip {
+    int state = CLIP_NONE;              // CLIP_ROWS: s2a_run's arrays stand, nothing counted yet
+    S2ADevRows rows{};                  // what s2a_run's kernels read
+    std::vector<int32_t> name;          // per (reference, position) with a count > 0, by
+    std::vector<int64_t> pos;           //   (name as Python sorts str, pos): index into
+    std::vector<int32_t> count;         //   S2AState::names, 1-based position, units
+    std::string text;                   // clipping.csv, formatted on first use
+    bool text_valid = false;
+    int64_t *d_lo = nullptr, *d_base = nullptr;              // per reference: window start, offset in d_diff
+    int32_t *d_wlen = nullptr, *d_diff = nullptr, *d_idx = nullptr, *d_cnt = nullptr,
+            *d_n = nullptr;                                  // d_n: pairs per reference, then the error flag
+};
+
 struct S2AState {
     // ---- rows of the last remap.csv (host) ----
     int64_t n_rows = 0;
@@ -97,6 +126,7 @@ struct S2AState {
     int64_t wr_bytes = -1;
     // ---- host timings of the last call (ms) ----
     double t_parse = 0, t_device = 0, t_format[3] = {0, 0, 0};
+    S2AClip clip;
     // ---- this rank's part of a sharded sam2aln ----
     S2AShard *shard = nullptr;
     ~S2AState() { if (shard) s2a_shard_free(shard); }
@@ -122,6 +152,8 @@ inline void s2a_begin(Ctx &c, S2AState &S)
     S.wr_bytes = -1;
     S.n_merge = S.n_unique = 0;
     S.res.clear();
+    S.clip.state = CLIP_NONE;
+    S.clip.text_valid = false;
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
     S.out_valid = 0;
 }
@@ -140,17 +172,11 @@ int s2a_format(S2AState &S, int which, std::vector<std::string> &out);
 // crc (may be null): the crc32 of the bytes written, from the pieces' own
 int s2a_format_write(S2AState &S, int which, int fd, int64_t offset, int64_t *written,
                      uint32_t *crc = nullptr);
-// device half.  dev: the row arrays are on the device already (k_s2a_stage
-// wrote them) and span[r] is row r's reference span; without it they are
-// uploaded from S and the spans come from S.cig
-struct S2ADevRows {
-    const uint8_t *seq, *qual;
-    const int64_t *soff;
-    const int32_t *pos, *cig_off, *n_cig;
-    const uint32_t *cig;
-    const int32_t *span;                // host: S2AState::d_spanins per row
-};
+// device half (S2ADevRows above)
 int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev = nullptr);
+// k_s2a_clip and k_s2a_clip_scan over the units of the last s2a_run, once per
+// call: S.clip's (name, pos, count) lists
+int s2a_clip_run(Ctx &c, S2AState &S);
 // Units, failure causes, group names and QNAMEs of the resident rows (one
 // per read, in read order) instead of s2a_parse: S.pos, S.flag, S.n_cig,
 // S.cig_off and S.cig hold the rows as k_s2a_stage wrote them; sam_ref[r]

@@ -22,6 +22,9 @@
 //   k_s2a_stage   mh_sam2aln_resident: the rows k_s2a_merge reads, built from
 //                 the resident packed reads and the last mapping pass's
 //                 records instead of parsed from remap.csv and uploaded
+//   k_s2a_clip, k_s2a_clip_scan   only when mh_sam2aln_clipping asks: the
+//                 positions each merged unit soft-clips and no mate aligns,
+//                 counted per reference (clipping.csv; no reference code)
 // Bit-for-bit specification: the reference itself (tests/golden/e2e/*/aligned.csv
 // etc. were produced by running micall.core.sam2aln on the same remap.csv).
 #include <fcntl.h>
@@ -39,6 +42,7 @@
 
 #include "mh_gunzip.h"
 #include "mh_sam2aln.h"
+#include "mh_text.h"
 
 namespace mh {
 
@@ -58,6 +62,12 @@ static void s2a_free_device(S2AState &S)
         S.d_uniq = S.d_ctr = nullptr;
     S.d_cig = nullptr;
     S.d_h = S.d_tkey = nullptr;
+    S2AClip &K = S.clip;
+    hipFree(K.d_lo); hipFree(K.d_base); hipFree(K.d_wlen); hipFree(K.d_diff); hipFree(K.d_idx);
+    hipFree(K.d_cnt); hipFree(K.d_n);
+    K.d_lo = K.d_base = nullptr;
+    K.d_wlen = K.d_diff = K.d_idx = K.d_cnt = K.d_n = nullptr;
+    K.state = CLIP_NONE;
     S.dcap.clear();
 }
 
@@ -661,7 +671,10 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
     S.uniq.clear();
     S.uniq_off.clear();
     S.gathered.clear();
-    if (S.n_merge == 0) return 0;
+    if (S.n_merge == 0) {
+        S.clip.state = CLIP_ROWS;    // no unit to count: clipping.csv is its header
+        return 0;
+    }
     if (S.n_merge * nc > 0x7f7f7f7f) {   // entries are int32 in the table and in uniq
         set_error("sam2aln: %lld pairs at %d q-cutoffs are too many merge entries",
                   (long long)S.n_merge, nc);
@@ -778,6 +791,339 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
         MH_HIP(hipStreamSynchronize(s));
     }
     prof_flush(c);
+    // d_units / d_uref and these rows stand until the next call: s2a_clip_run
+    S.clip.rows = dev ? *dev : S2ADevRows{S.d_seq, S.d_qual, S.d_soff, S.d_pos, S.d_cigoff, S.d_ncig,
+                                          S.d_cig, nullptr};
+    S.clip.state = CLIP_ROWS;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Soft-clip counts (clipping.csv; DESIGN.md section 6, "Soft-clip counts").
+// Per read with 1-based POS p: lead = the S ops before the first other op,
+// trail = every other S op, span = M + D; clipped = [p - lead, p) and
+// [p + span, p + span + trail), mapped = [p, p + span).  A merged unit adds 1
+// at every position some mate clips and no mate aligns.
+//
+// k_s2a_clip       one thread per unit: the <= 12 interval ends of its mates,
+//                  and at each distinct end x the step in(x) - in(x - 1) of
+//                  "clipped and not mapped" (+1 where it begins, -1 where it
+//                  ends) added to the reference's difference array at
+//                  x - lo[ref].  An amplicon puts nearly every unit's steps on
+//                  the same few addresses, so a block first sums them in an
+//                  LDS table keyed by the array index (CLIP_SLOTS slots,
+//                  CLIP_PROBES probes, then straight to HBM) and flushes one
+//                  atomic per slot it used.  Integer adds: no order matters.
+// k_s2a_clip_scan  one block per reference: the running sum over its window
+//                  in chunks of the block's size (wave scans, wave totals in
+//                  LDS, a carry between chunks), and the non-zero sums
+//                  compacted in position order by a second scan of flags.
+// ---------------------------------------------------------------------------
+constexpr int CLIP_SLOTS = 1024;    // LDS table of k_s2a_clip (12 KiB a block)
+constexpr int CLIP_PROBES = 8;
+constexpr int CLIP_UNITS_PER_THREAD = 16;
+
+struct ClipArgs {
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int64_t *units;     // per merge unit: row1, row2 (-1: single)
+    const int32_t *uref;
+    int64_t n;
+    const int64_t *lo, *base; // per reference: first position of its window, its offset in diff
+    const int32_t *wlen;      // per reference: positions in its window (diff holds wlen + 1)
+    int32_t *diff;
+    int32_t *err;             // set when a step falls outside its window
+    int lds;                  // 0: every step straight to HBM (measurements)
+};
+
+struct ClipUnit {
+    int64_t cl[4], ch[4];     // clipped [cl, ch): lead and trail of each mate
+    int64_t ml[2], mh[2];     // mapped [ml, mh)
+};
+
+__device__ __forceinline__ void clip_read(const ClipArgs &A, int64_t r, ClipUnit &U, int k)
+{
+    const int nc = A.n_cig[r];
+    const uint32_t *ops = A.cig + A.cig_off[r];
+    int64_t lead = 0, trail = 0, span = 0;
+    bool head = true;
+    for (int o = 0; o < nc; ++o) {
+        const uint32_t op = ops[o];
+        const int64_t n = (int64_t)(op >> 4);
+        const int t = (int)(op & 15);
+        if (t == MH_OP_S) {
+            if (head) lead += n; else trail += n;
+        } else {
+            head = false;
+            if (t == MH_OP_M || t == MH_OP_D) span += n;
+        }
+    }
+    const int64_t p = A.pos[r];
+    U.cl[2 * k] = p - lead;       U.ch[2 * k] = p;
+    U.cl[2 * k + 1] = p + span;   U.ch[2 * k + 1] = p + span + trail;
+    U.ml[k] = p;                  U.mh[k] = p + span;
+}
+
+__device__ __forceinline__ int clip_in(const ClipUnit &U, int64_t y)
+{
+    bool c = false, m = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c |= y >= U.cl[k] && y < U.ch[k];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) m |= y >= U.ml[k] && y < U.mh[k];
+    return c && !m;
+}
+
+__device__ __forceinline__ void clip_add(const ClipArgs &A, unsigned long long *tkey, int32_t *tval,
+                                         int ref, int64_t x, int d)
+{
+    const int64_t idx = x - A.lo[ref];
+    if (idx < 0 || idx > (int64_t)A.wlen[ref]) {   // the host sized the window from the same rows
+        atomicExch(A.err, 1);
+        return;
+    }
+    const int64_t g = A.base[ref] + idx;
+    if (A.lds) {
+        const unsigned long long key = (unsigned long long)g + 1ull;
+        unsigned s = (unsigned)hash_key(key) & (CLIP_SLOTS - 1);
+        for (int t = 0; t < CLIP_PROBES; ++t, s = (s + 1) & (CLIP_SLOTS - 1)) {
+            const unsigned long long old = atomicCAS(&tkey[s], 0ull, key);
+            if (old == 0ull || old == key) {
+                atomicAdd(&tval[s], d);
+                return;
+            }
+        }
+    }
+    atomicAdd(&A.diff[g], d);
+}
+
+__global__ __launch_bounds__(256) void k_s2a_clip(ClipArgs A)
+{
+    __shared__ unsigned long long tkey[CLIP_SLOTS];
+    __shared__ int32_t tval[CLIP_SLOTS];
+    for (int s = threadIdx.x; s < CLIP_SLOTS; s += blockDim.x) { tkey[s] = 0ull; tval[s] = 0; }
+    __syncthreads();
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < A.n;
+         u += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r1 = A.units[2 * u], r2 = A.units[2 * u + 1];
+        ClipUnit U;
+        clip_read(A, r1, U, 0);
+        if (r2 >= 0) {
+            clip_read(A, r2, U, 1);
+        } else {
+            U.cl[2] = U.ch[2] = U.cl[3] = U.ch[3] = U.ml[1] = U.mh[1] = 0;   // empty
+        }
+        const int ref = A.uref[u];
+        // every index below is a constant once unrolled: e[] stays in registers
+        int64_t e[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { e[k] = U.cl[k]; e[4 + k] = U.ch[k]; }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { e[8 + k] = U.ml[k]; e[10 + k] = U.mh[k]; }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            bool dup = false;
+#pragma unroll
+            for (int j = 0; j < i; ++j) dup |= e[j] == e[i];
+            const int d = clip_in(U, e[i]) - clip_in(U, e[i] - 1);
+            if (!dup && d) clip_add(A, tkey, tval, ref, e[i], d);
+        }
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < CLIP_SLOTS; s += blockDim.x)
+        if (tkey[s] && tval[s]) atomicAdd(&A.diff[tkey[s] - 1ull], tval[s]);
+}
+
+__global__ __launch_bounds__(1024) void k_s2a_clip_scan(const int64_t *base, const int32_t *wlen,
+                                                        int32_t *diff, int32_t *idx_out,
+                                                        int32_t *cnt_out, int32_t *n_out)
+{
+    __shared__ int32_t wsum[16], wnz[16];
+    const int ref = blockIdx.x;
+    const int64_t b = base[ref];
+    const int n = wlen[ref] + 1;           // 0 for a reference without units (wlen -1)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int carry = 0, outn = 0;
+    for (int i0 = 0; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + (int)threadIdx.x;
+        const int v = i < n ? diff[b + i] : 0;
+        const int s = s2a_scan(v, lane);
+        if (lane == 63) wsum[wv] = s;
+        __syncthreads();
+        int pre = 0, tot = 0;
+        for (int w = 0; w < nw; ++w) { const int t = wsum[w]; pre += w < wv ? t : 0; tot += t; }
+        const int cov = carry + pre + s;
+        const int nz = i < n && cov != 0;
+        const int f = s2a_scan(nz, lane);
+        if (lane == 63) wnz[wv] = f;
+        __syncthreads();
+        int pre2 = 0, tot2 = 0;
+        for (int w = 0; w < nw; ++w) { const int t = wnz[w]; pre2 += w < wv ? t : 0; tot2 += t; }
+        if (i < n) diff[b + i] = cov;
+        if (nz) {
+            const int k = outn + pre2 + f - 1;     // < n: one pair per position at most
+            idx_out[b + k] = i;
+            cnt_out[b + k] = cov;
+        }
+        carry += tot;
+        outn += tot2;
+        __syncthreads();                   // wsum / wnz are rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) n_out[ref] = outn;
+}
+
+int s2a_clip_run(Ctx &c, S2AState &S)
+{
+    S2AClip &K = S.clip;
+    if (K.state == CLIP_DONE) return 0;
+    if (K.state != CLIP_ROWS) {
+        set_error("sam2aln clipping: no rows of a sam2aln call are on the device");
+        return -3;
+    }
+    // the resident rows' CIGARs are the mapping pass's pool itself
+    if (S.n_merge && K.rows.cig != S.d_cig && (!c.map.valid || K.rows.cig != c.map.pool)) {
+        set_error("sam2aln clipping: the mapping pass the rows came from is gone");
+        return -3;
+    }
+    K.name.clear(); K.pos.clear(); K.count.clear();
+    K.text_valid = false;
+    const int nref = (int)S.names.size();
+    const int64_t nu = (int64_t)S.u1.size();
+    // ---- each reference's window from its units' rows: POS - lead .. POS + span + trail ----
+    std::vector<int64_t> lo((size_t)nref, INT64_MAX), hi((size_t)nref, INT64_MIN);
+    for (int64_t u = 0; u < nu; ++u) {
+        if (S.ucause[u] >= 0) continue;
+        const int g = S.name_id[u];
+        for (int64_t r : {S.u1[u], S.upaired[u] ? S.u2[u] : (int64_t)-1}) {
+            if (r < 0) continue;
+            int64_t lead = 0, rest = 0;
+            bool head = true;
+            for (int o = 0; o < S.n_cig[r]; ++o) {
+                const uint32_t op = S.cig[S.cig_off[r] + o];
+                const int t = (int)(op & 15);
+                if (t == MH_OP_S && head) { lead += op >> 4; continue; }
+                head = false;
+                if (t == MH_OP_S || t == MH_OP_M || t == MH_OP_D) rest += op >> 4;
+            }
+            lo[g] = std::min(lo[g], (int64_t)S.pos[r] - lead);
+            hi[g] = std::max(hi[g], (int64_t)S.pos[r] + rest);
+        }
+    }
+    std::vector<int64_t> base((size_t)nref + 1, 0);
+    std::vector<int32_t> wlen((size_t)nref, -1);
+    for (int g = 0; g < nref; ++g) {
+        if (lo[g] > hi[g]) { lo[g] = 0; base[g + 1] = base[g]; continue; }
+        if (hi[g] - lo[g] > S2A_CLIP_MAX_WINDOW) {
+            set_error("sam2aln clipping: the rows of %s span positions %lld to %lld, more than %lld",
+                      S.names[g].c_str(), (long long)lo[g], (long long)hi[g],
+                      (long long)S2A_CLIP_MAX_WINDOW);
+            return -3;
+        }
+        wlen[g] = (int32_t)(hi[g] - lo[g]);
+        base[g + 1] = base[g] + wlen[g] + 1;
+    }
+    const int64_t total = base[nref];
+    if (S.n_merge == 0 || total == 0) { K.state = CLIP_DONE; return 0; }
+    hipStream_t s = c.stream;
+    if (int st = s2a_upload(S, K.d_lo, lo, s)) return st;
+    if (int st = s2a_upload(S, K.d_base, base, s)) return st;
+    if (int st = s2a_upload(S, K.d_wlen, wlen, s)) return st;
+    if (int st = dev_reserve(S, K.d_diff, sizeof(int32_t) * (size_t)total)) return st;
+    if (int st = dev_reserve(S, K.d_idx, sizeof(int32_t) * (size_t)total)) return st;
+    if (int st = dev_reserve(S, K.d_cnt, sizeof(int32_t) * (size_t)total)) return st;
+    if (int st = dev_reserve(S, K.d_n, sizeof(int32_t) * ((size_t)nref + 1))) return st;
+    MH_HIP(hipMemsetAsync(K.d_diff, 0, sizeof(int32_t) * (size_t)total, s));
+    MH_HIP(hipMemsetAsync(K.d_n, 0, sizeof(int32_t) * ((size_t)nref + 1), s));
+    static const bool lds = !(getenv("MICALL_CLIP_LDS") && *getenv("MICALL_CLIP_LDS") == '0');
+    ClipArgs a{K.rows.pos, K.rows.cig_off, K.rows.n_cig, K.rows.cig, S.d_units, S.d_uref, S.n_merge,
+               K.d_lo, K.d_base, K.d_wlen, K.d_diff, K.d_n + nref, lds ? 1 : 0};
+    int64_t blocks = (S.n_merge + 256 * CLIP_UNITS_PER_THREAD - 1) / (256 * CLIP_UNITS_PER_THREAD);
+    if (blocks > 4096) blocks = 4096;
+    const int p0 = prof_begin(c, "k_s2a_clip");
+    hipLaunchKernelGGL(k_s2a_clip, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    prof_end(c, p0);
+    MH_HIP(hipGetLastError());
+    const int p1 = prof_begin(c, "k_s2a_clip_scan");
+    hipLaunchKernelGGL(k_s2a_clip_scan, dim3((unsigned)nref), dim3(1024), 0, s, K.d_base, K.d_wlen,
+                       K.d_diff, K.d_idx, K.d_cnt, K.d_n);
+    prof_end(c, p1);
+    MH_HIP(hipGetLastError());
+    std::vector<int32_t> n_out((size_t)nref + 1);
+    MH_HIP(hipMemcpyAsync(n_out.data(), K.d_n, sizeof(int32_t) * n_out.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    prof_flush(c);
+    if (n_out[nref]) {
+        set_error("sam2aln clipping: a clipped position fell outside its reference's window");
+        return -4;
+    }
+    // ---- the pairs of each reference, references as Python sorts str ----
+    std::vector<int> order((size_t)nref);
+    for (int g = 0; g < nref; ++g) order[g] = g;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return S.names[x] < S.names[y]; });
+    std::vector<int64_t> at((size_t)nref + 1, 0);
+    for (int k = 0; k < nref; ++k) {
+        const int g = order[k];
+        if (n_out[g] < 0 || n_out[g] > wlen[g] + 1) {
+            set_error("sam2aln clipping: %d positions counted in a window of %d", n_out[g], wlen[g] + 1);
+            return -4;
+        }
+        at[k + 1] = at[k] + n_out[g];
+    }
+    std::vector<int32_t> idx((size_t)at[nref]);
+    K.count.resize((size_t)at[nref]);
+    for (int k = 0; k < nref; ++k) {
+        const int g = order[k];
+        if (!n_out[g]) continue;
+        const size_t nb = sizeof(int32_t) * (size_t)n_out[g];
+        MH_HIP(hipMemcpyAsync(idx.data() + at[k], K.d_idx + base[g], nb, hipMemcpyDeviceToHost, s));
+        MH_HIP(hipMemcpyAsync(K.count.data() + at[k], K.d_cnt + base[g], nb, hipMemcpyDeviceToHost, s));
+    }
+    MH_HIP(hipStreamSynchronize(s));
+    K.name.resize(idx.size());
+    K.pos.resize(idx.size());
+    for (int k = 0; k < nref; ++k)
+        for (int64_t j = at[k]; j < at[k + 1]; ++j) {
+            K.name[j] = order[k];
+            K.pos[j] = lo[order[k]] + idx[j];
+        }
+    K.state = CLIP_DONE;
+    return 0;
+}
+
+// clipping.csv of S.clip's lists: refname,pos,count
+static void s2a_clip_text(S2AState &S)
+{
+    S2AClip &K = S.clip;
+    if (K.text_valid) return;
+    std::string &o = K.text;
+    o.assign("refname,pos,count\n");
+    for (size_t j = 0; j < K.name.size(); ++j) {
+        const std::string &rn = S.names[K.name[j]];
+        csv_field(o, rn.data(), rn.size());
+        o.push_back(',');
+        o += std::to_string((long long)K.pos[j]);
+        o.push_back(',');
+        o += std::to_string(K.count[j]);
+        o.push_back('\n');
+    }
+    K.text_valid = true;
+}
+
+// the counts of the context's last sam2aln call, counted now if not yet
+static int s2a_clip_of(mh_ctx *ctx, const char *what, bool text, S2AState **out)
+{
+    Ctx &c = *ctx_of(ctx);
+    if (!c.s2a) { set_error("%s: no sam2aln results", what); return -3; }
+    MH_HIP(hipSetDevice(c.device));
+    try {
+        if (int st = s2a_clip_run(c, *c.s2a)) return st;
+        if (text) s2a_clip_text(*c.s2a);
+    } catch (const std::exception &e) {
+        c.s2a->clip.text_valid = false;
+        set_error("%s: out of memory (%s)", what, e.what());
+        return -2;
+    }
+    *out = c.s2a;
     return 0;
 }
 
@@ -1108,6 +1454,51 @@ extern "C" int mh_sam2aln_output(mh_ctx *ctx, int which, char *buf, size_t cap, 
     for (const std::string &p : out) { memcpy(buf, p.data(), p.size()); buf += p.size(); }
     std::vector<std::string>().swap(out);   // handed over: free the cached text
     S.out_valid &= ~(1 << which);
+    return 0;
+}
+
+extern "C" int mh_sam2aln_clipping(mh_ctx *ctx, char *buf, size_t cap, size_t *used)
+{
+    if (!ctx || !used) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_clip_of(ctx, "mh_sam2aln_clipping", true, &S)) return st;
+    const std::string &t = S->clip.text;
+    *used = t.size();
+    if (!buf) return 0;
+    if (cap < t.size()) { set_error("mh_sam2aln_clipping: buffer too small"); return -2; }
+    memcpy(buf, t.data(), t.size());
+    return 0;
+}
+
+extern "C" int mh_sam2aln_clipping_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written)
+{
+    if (!ctx || fd < 0 || offset < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_clip_of(ctx, "mh_sam2aln_clipping_write", true, &S)) return st;
+    const std::string &t = S->clip.text;
+    if (const int e = write_all_at(fd, t.data(), t.size(), offset)) {
+        set_error("mh_sam2aln_clipping_write: write failed (%s)", strerror(e));
+        return -4;
+    }
+    if (written) *written = (int64_t)t.size();
+    return 0;
+}
+
+extern "C" int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *count,
+                                      int64_t cap, int64_t *n)
+{
+    if (!ctx || !n || cap < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_clip_of(ctx, "mh_sam2aln_clip_counts", false, &S)) return st;
+    const S2AClip &K = S->clip;
+    *n = (int64_t)K.name.size();
+    if (!name_id || !pos || !count) return 0;
+    if (cap < *n) { set_error("mh_sam2aln_clip_counts: buffer too small"); return -2; }
+    if (*n) {
+        memcpy(name_id, K.name.data(), sizeof(int32_t) * K.name.size());
+        memcpy(pos, K.pos.data(), sizeof(int64_t) * K.pos.size());
+        memcpy(count, K.count.data(), sizeof(int32_t) * K.count.size());
+    }
     return 0;
 }
 

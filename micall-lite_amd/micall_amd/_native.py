@@ -145,6 +145,10 @@ def _declare(L):
         'mh_sam2aln_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_double, _I64P], ctypes.c_int),
         'mh_sam2aln_write': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_stats': ([_P, _P], ctypes.c_int),
+        'mh_sam2aln_clipping': ([_P, ctypes.c_char_p, ctypes.c_size_t,
+                                 ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_sam2aln_clipping_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
+        'mh_sam2aln_clip_counts': ([_P, _P, _P, _P, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_written': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _I64P], ctypes.c_int),
         'mh_sam2aln_serial': ([_P, _I64P], ctypes.c_int),
         'mh_a2c_load_resident': ([_P, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
@@ -649,6 +653,40 @@ class Context:
               'mh_sam2aln_output')
         del cbuf
         return buf.decode()
+
+    def sam2aln_clipping(self):
+        """clipping.csv text of the last sam2aln call (mh_sam2aln_clipping):
+        per reference and position the units that soft-clip it while no mate
+        aligns it.  The device pass runs on the first request."""
+        used = ctypes.c_size_t()
+        check(lib().mh_sam2aln_clipping(self.h, None, 0, ctypes.byref(used)), 'mh_sam2aln_clipping')
+        buf = bytearray(used.value)
+        cbuf = (ctypes.c_char * len(buf)).from_buffer(buf)
+        check(lib().mh_sam2aln_clipping(self.h, cbuf, len(buf), ctypes.byref(used)), 'mh_sam2aln_clipping')
+        del cbuf
+        return buf.decode()
+
+    def sam2aln_clipping_write(self, fd, offset):
+        """clipping.csv written to fd at offset (pwrite); bytes written."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_clipping_write(self.h, int(fd), int(offset), ctypes.byref(n)),
+              'mh_sam2aln_clipping_write')
+        return n.value
+
+    def sam2aln_clip_counts(self):
+        """(name ids int32, positions int64, counts int32) of clipping.csv's
+        rows (mh_sam2aln_clip_counts); a name id indexes the call's reference
+        names in first-seen order (sam2aln_part_names)."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_clip_counts(self.h, None, None, None, 0, ctypes.byref(n)),
+              'mh_sam2aln_clip_counts')
+        ids = np.empty(n.value, dtype=np.int32)
+        pos = np.empty(n.value, dtype=np.int64)
+        cnt = np.empty(n.value, dtype=np.int32)
+        if n.value:
+            check(lib().mh_sam2aln_clip_counts(self.h, _ptr(ids), _ptr(pos), _ptr(cnt), n.value,
+                                               ctypes.byref(n)), 'mh_sam2aln_clip_counts')
+        return ids, pos, cnt
 
     @staticmethod
     def _bad_cycle_args(bad_cycles):

@@ -72,6 +72,8 @@ MAX_CUTOFF = 'MAX'
 _SCHEMA = {
     'amino': ['seed', 'region', 'q-cutoff', 'query.aa.pos', 'refseq.aa.pos'] + list(AMINO_ALPHABET),
     'nuc': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT'),
+    'nuc_detail': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
+                  ['N', 'del', 'clip', 'coverage'],
     'conseq': ['region', 'q-cutoff', 'consensus-percent-cutoff', 'offset', 'sequence'],
     'nuc_variants': ['seed', 'qcut', 'region', 'index', 'count', 'seq'],
     'failed': ['seed', 'region', 'qcut', 'queryseq', 'refseq'],
@@ -503,6 +505,9 @@ class SequenceReport(object):
     def write_failure_header(self, fail_file):
         _csv_writer(fail_file, 'failed').writeheader()
 
+    def write_nuc_detail_header(self, nuc_detail_file):
+        _csv_writer(nuc_detail_file, 'nuc_detail').writeheader()
+
     # ---- bodies ----
     def write_amino_counts(self, amino_file, coverage_summary=None):
         """Amino-acid counts per coordinate position, regions in name order;
@@ -522,27 +527,51 @@ class SequenceReport(object):
                     coverage_summary.update(avg_coverage=mean, coverage_region=name,
                                             region_width=len(cmap))
 
-    def write_nuc_counts(self, nuc_file):
-        """A/C/G/T counts per nucleotide: in coordinate positions, or in seed
-        positions when the seed has no coordinate region."""
-        out = csv.writer(nuc_file, lineterminator=os.linesep)
-        lines = []
+    def _nuc_lines(self, classes):
+        """nuc.csv's rows with the first `classes` of the A C G T N - counts
+        of each nucleotide (in coordinate positions, or in seed positions when
+        the seed has no coordinate region), and per row the reading frame of
+        its region's map."""
+        lines, frames = [], []
         if not self.coordinate_refs:
             n = len(self.seed_aminos[0])      # KeyError without reads, as the reference
             frame = self._frames[0]
-            counts = np.zeros((n, 3, 4), dtype=np.int64)
-            counts[:frame.ncod] = frame.nt_cnt[:, :, :4]
+            counts = np.zeros((n, 3, classes), dtype=np.int64)
+            counts[:frame.ncod] = frame.nt_cnt[:, :, :classes]
             for codon, per_base in enumerate(counts.tolist()):
                 lines.extend([self.seed, self.seed, self.qcut, 3 * codon + t + 1, ''] + acgt
                              for t, acgt in enumerate(per_base))
+            frames = [0] * len(lines)
         else:
             for name, cmap in ((n, self._coord_maps[n]) for n in self.reports):
-                counts = self._gather(cmap, lambda fr: fr.nt_cnt[:, :, :4], (3, 4))
+                counts = self._gather(cmap, lambda fr: fr.nt_cnt[:, :, :classes], (3, classes))
                 for k, pos, per_base in zip(cmap.conseq_index.tolist(), cmap.positions.tolist(),
                                             counts.tolist()):
                     lines.extend([self.seed, name, self.qcut, '' if k < 0 else 3 * k + t + 1,
                                   3 * pos - 2 + t] + acgt for t, acgt in enumerate(per_base))
-        out.writerows(lines)
+                frames += [cmap.frame] * (3 * len(cmap))
+        return lines, frames
+
+    def write_nuc_counts(self, nuc_file):
+        """A/C/G/T counts per nucleotide: in coordinate positions, or in seed
+        positions when the seed has no coordinate region."""
+        csv.writer(nuc_file, lineterminator=os.linesep).writerows(self._nuc_lines(4)[0])
+
+    def write_nuc_detail(self, nuc_detail_file, clipping=None):
+        """nuc.csv's rows (not in the reference) followed by what they leave
+        out: the N and deletion counts of the position, the units that
+        soft-clip it, and coverage = A + C + G + T + N + del, the depth
+        write_consensus tests against min_coverage.  clipping: {seed:
+        {consensus position: count}} of sam2aln's clipping.csv, None to leave
+        the clip column empty.  query.nuc.pos ignores the reading frame, so
+        the consensus position of a row is query.nuc.pos - frame."""
+        lines, frames = self._nuc_lines(6)
+        clips = None if clipping is None else clipping.get(self.seed, {})
+        for line, f in zip(lines, frames):
+            query = line[3]
+            clip = '' if clips is None else 0 if query == '' else clips.get(query - f, 0)
+            line[11:] = [clip, sum(line[5:11])]
+        csv.writer(nuc_detail_file, lineterminator=os.linesep).writerows(lines)
 
     def write_consensus(self, conseq_file, min_coverage=100):
         """The nucleotide consensus of frame 0 from its first counted codon
@@ -795,13 +824,17 @@ _SHARD = None      # the job's Shard while a sharded aln2counts runs (InsertionW
 
 def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
-               coverage_summary_csv=None, json=None, variants_csv=None):
+               coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
+               nuc_detail_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
     variants_csv takes the top nucleotide variants of every coordinate region
     (SequenceReport.write_variants); nuc_variants_csv fails as the
-    reference's does.
+    reference's does.  nuc_detail_csv takes nuc.csv's rows with the N,
+    deletion, soft-clip and coverage counts (SequenceReport.write_nuc_detail);
+    clipping_csv is the input its clip column comes from, sam2aln's
+    clipping.csv (None: the column stays empty).
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -817,7 +850,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     SHARD_STATS.clear()
     session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
-               coverage_summary_csv, variants_csv)
+               coverage_summary_csv, variants_csv, nuc_detail_csv)
     with session.writer_stage(*handles) as stage:
         split = sh is not None
         if split:
@@ -830,14 +863,16 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
             if stage.active:
                 _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
-                            variants_csv=variants_csv)
+                            variants_csv=variants_csv, clipping_csv=clipping_csv,
+                            nuc_detail_csv=nuc_detail_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
         _SHARD = sh
         try:
             _aln2counts(aligned_csv, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5],
-                        callback if stage.active else None, outs[6], json, groups=groups)
+                        callback if stage.active else None, outs[6], json, groups=groups,
+                        clipping_csv=clipping_csv, nuc_detail_csv=outs[8])
         finally:
             _SHARD = None
 
@@ -899,7 +934,7 @@ def _load_sharded(sh, aligned_csv):
 
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
-                variants_csv=None):
+                variants_csv=None, clipping_csv=None, nuc_detail_csv=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -919,6 +954,10 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if variants_csv is not None:
         report.write_nuc_variants_header(variants_csv)
         per_run.append(lambda: report.write_variants(variants_csv))
+    if nuc_detail_csv is not None:
+        clipping = None if clipping_csv is None else _read_clipping(clipping_csv)
+        report.write_nuc_detail_header(nuc_detail_csv)
+        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -953,6 +992,14 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
         summary_writer.writerow(summary)
 
 
+def _read_clipping(clipping_csv):
+    """{refname: {pos: count}} of sam2aln's clipping.csv."""
+    clipping = {}
+    for row in csv.DictReader(clipping_csv):
+        clipping.setdefault(row['refname'], {})[int(row['pos'])] = int(row['count'])
+    return clipping
+
+
 def _arguments():
     cli = argparse.ArgumentParser(description='aln2counts on the MI355X: counts, consensus and '
                                               'insertions from aligned.csv.')
@@ -967,6 +1014,10 @@ def _arguments():
                      help='output: nucleotide variants')
     cli.add_argument('--variants_csv', type=argparse.FileType('w'),
                      help='output: top nucleotide variants of every coordinate region')
+    cli.add_argument('--clipping_csv', type=argparse.FileType('r'),
+                     help="input: sam2aln's clipping.csv, for the clip column of nuc_detail_csv")
+    cli.add_argument('--nuc_detail_csv', type=argparse.FileType('w'),
+                     help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
     return cli.parse_args()
 
 
@@ -976,7 +1027,8 @@ parseArgs = _arguments
 def main():
     a = _arguments()
     aln2counts(a.aligned_csv, a.nuc_csv, a.amino_csv, a.coord_ins_csv, a.conseq_csv,
-               a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv)
+               a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv,
+               clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv)
 
 
 if __name__ == '__main__':

@@ -30,6 +30,12 @@ sequences are counted by hash owner and sorted across the ranks by a sample
 sort (_sam2aln_sharded, mh_s2a_shard.cpp) -- the reference's own pool splits
 parse_sam over pairs the same way (sam2aln.py:411-424).  The split takes one
 q-cutoff; with more, rank 0 does the whole stage.
+
+clipping_csv (optional, not in the reference): per consensus position the
+number of merged units that soft-clip it while no mate aligns it
+(refname,pos,count), counted on the device from the rows the merge left
+there (mh_sam2aln_clipping: k_s2a_clip, k_s2a_clip_scan) on every route.
+A call without it launches and allocates nothing for it.
 """
 import argparse
 import os
@@ -62,21 +68,24 @@ def _cutoff_list(q_cutoffs):
     return cuts
 
 
-def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None):
+def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None,
+            clipping_csv=None):
     """sam2aln.sam2aln (sam2aln.py:395-478).  q_cutoffs: the list of quality
     cutoffs, None for the module's SAM2ALN_Q_CUTOFFS (where the reference's
     users set it).  In a sharded job every rank does its share
     (_sam2aln_sharded); when remap.csv cannot be split that way, rank 0
-    computes and writes while the other ranks wait (session.writer_stage)."""
+    computes and writes while the other ranks wait (session.writer_stage).
+    clipping_csv: an open file for the soft-clip counts, None for none."""
     cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
     session.stats['sam2aln_source'] = 'csv'
     session.aligned_forget()     # recorded again below, once aligned.csv is these results
     use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
-    if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts):
+    if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts,
+                                           clipping_csv):
         return
-    with session.writer_stage(aligned_csv, insert_csv, failed_csv) as stage:
+    with session.writer_stage(aligned_csv, insert_csv, failed_csv, clipping_csv) as stage:
         if not stage.active:
             return
         ctx = session.context()
@@ -94,6 +103,8 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
         if done is None:
             text = session.read_text(remap_csv)
             ctx.sam2aln_csv(text, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
+        if clipping_csv:
+            _write_clipping(ctx, clipping_csv)
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
                 start = _write_output(ctx, which, handle)
@@ -104,7 +115,7 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
 SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitters
 
 
-def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None):
+def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None, clipping_csv=None):
     """This rank's share of sam2aln.  False (on every rank, before any
     output is written) when the job must fall back to rank 0 alone: more
     than one q-cutoff (every rank holds the same list, so none has to ask),
@@ -134,6 +145,8 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
     # reference names in the reference's first-seen order over the job's
     # units: every rank's pair units in rank order, then every rank's leftovers
     names, first = ctx.sam2aln_part_names(part['names'])
+    if clipping_csv:
+        _clipping_sharded(sh, ctx, names, clipping_csv)
     texts = sh.all_gather_bytes('\n'.join(names).encode())
     firsts = sh.all_gather_bytes(np.asarray(first, dtype=np.int64).tobytes())
     pairs = sh._gather_sizes([part['pair_units']])[:, 0]
@@ -180,10 +193,45 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
             o.finish()
     out.finish()
     sh.barrier()             # every rank's rows are in the files
-    for h in (aligned_csv, insert_csv, failed_csv):
+    for h in (aligned_csv, insert_csv, failed_csv, clipping_csv):
         if h and sh.rank == 0:
             h.flush()
     return True
+
+
+def _clipping_sharded(sh, ctx, names, clipping_csv):
+    """clipping.csv of a sharded call: every rank counts the units of its
+    own rows on its device, the (name, pos, count) lists are all-gathered,
+    and rank 0 sums them and writes (the barrier at the end of the stage
+    holds the other ranks until it has)."""
+    import csv
+    ids, pos, cnt = ctx.sam2aln_clip_counts()
+    mine = '\n'.join(names).encode(), ids.tobytes(), pos.tobytes(), cnt.tobytes()
+    parts = [sh.all_gather_bytes(x) for x in mine]
+    if sh.rank != 0:
+        return
+    total = {}
+    for r in range(sh.world):
+        rn = parts[0][r].decode().split('\n') if parts[0][r] else []
+        for i, p, n in zip(np.frombuffer(parts[1][r], dtype=np.int32).tolist(),
+                           np.frombuffer(parts[2][r], dtype=np.int64).tolist(),
+                           np.frombuffer(parts[3][r], dtype=np.int32).tolist()):
+            key = rn[i], p
+            total[key] = total.get(key, 0) + n
+    w = csv.writer(clipping_csv, lineterminator='\n')
+    w.writerow(['refname', 'pos', 'count'])
+    w.writerows((name, p, total[name, p]) for name, p in sorted(total))
+
+
+def _write_clipping(ctx, handle):
+    """clipping.csv, as _write_output writes the other three."""
+    from .sharded_io import SharedOutput
+    out = SharedOutput(None, handle)
+    if out.direct:
+        out.end += ctx.sam2aln_clipping_write(out.fd, int(out.end))
+        out.finish()
+    else:
+        handle.write(ctx.sam2aln_clipping())
 
 
 def _write_output(ctx, which, handle):
@@ -232,13 +280,17 @@ def parseArgs():
     parser.add_argument('--qcut', type=int, action='append', default=None, metavar='Q',
                         help='quality cutoff of the merge; repeat it for several '
                              '(default: {})'.format(' '.join(map(str, SAM2ALN_Q_CUTOFFS))))
+    parser.add_argument('--clipping_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
+                        help='<output> CSV of soft-clipped positions that no mate aligns, '
+                             'counted per consensus position')
     return parser.parse_args()
 
 
 def main():
     args = parseArgs()
     sam2aln(remap_csv=args.remap_csv, aligned_csv=args.aligned_csv, insert_csv=args.insert_csv,
-            failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut)
+            failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut,
+            clipping_csv=args.clipping_csv)
 
 
 if __name__ == '__main__':
