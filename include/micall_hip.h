@@ -516,6 +516,29 @@ int mh_sam2aln_clipping_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *writ
  * mh_sam2aln_part_names prints).  *n = rows; arrays NULL: only *n. */
 int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *count, int64_t cap,
                            int64_t *n);
+/* conseq_ins.csv of the last sam2aln call on this context: the insertions
+ * that remap's last pass left out of the consensus, merged per unit as the
+ * reference's merge_inserts merges them and counted per distinct string
+ * (refname,qcut,pos,insert,count; names sorted as strings, then the cutoff,
+ * then pos, then count descending, then the string as bytes; '\n' line
+ * ends).  pos is the 0-based consensus coordinate of the base that follows
+ * the insertion (the 1-based position it follows; 0: before the first
+ * base), not insert.csv's read-derived pos.  A unit counts at the cutoffs at
+ * which it contributes a sequence to aligned.csv.  Nothing is computed
+ * before the first of these three calls asks: the pass (k_s2a_ins_rec,
+ * k_s2a_ins_merge, k_s2a_ins_tab and the merge's grouping kernels) then runs
+ * over the rows, units and merge results the call left on the device, so
+ * ask before the next sam2aln or mapping call.  buf NULL: only *used = bytes
+ * needed.  -3 with a message naming the read when an inserted byte is '-'. */
+int mh_sam2aln_conseq_ins(mh_ctx *ctx, char *buf, size_t cap, size_t *used);
+/* The same text written to fd at offset with pwrite; *written = its size. */
+int mh_sam2aln_conseq_ins_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written);
+/* Per (reference, cutoff, pos) the sum of conseq_ins.csv's counts over the
+ * strings, in the text's order: name_id as in mh_sam2aln_clip_counts,
+ * cut_index indexes the call's q-cutoffs as they were given.  *n = rows;
+ * arrays NULL: only *n. */
+int mh_sam2aln_ins_counts(mh_ctx *ctx, int32_t *name_id, int32_t *cut_index, int64_t *pos,
+                          int32_t *count, int64_t cap, int64_t *n);
 /* What the last mh_sam2aln_write of aligned.csv (which 0, the only one kept)
  * wrote: the crc32 of its text, joined from the formatted pieces' own
  * (nothing is read back), and its size.  -3 when this context's sam2aln

@@ -65,6 +65,35 @@ struct S2AClip {
             *d_n = nullptr;                                  // d_n: pairs per reference, then the error flag
 };
 
+// merged insertions of the last call (mh_sam2aln_conseq_ins), counted on the
+// first request from the same rows and units.  One record per (listed unit,
+// consensus key); one entry per (record, q-cutoff): entry = record * n_cut + k
+struct S2AInsRec {
+    int32_t unit, key;                  // merge unit; 0-based consensus coordinate the insertion precedes
+    int32_t len1, len2;                 // inserted bytes of mate 1 and mate 2 (0: none); both 0: unused record
+    int64_t src1, src2;                 // their first byte in seq / qual
+    int64_t boff;                       // the record's first merged byte, per cutoff
+};
+
+struct S2AIns {
+    bool done = false;
+    // conseq_ins.csv's rows in file order
+    std::vector<int32_t> name, cut, count;   // index into S2AState::names, index into q_cutoffs, units
+    std::vector<int64_t> pos, soff;          // the key; the string's place in strings (+ end)
+    std::string strings;
+    // per (name, cutoff, key) the sum over strings, in the same order
+    std::vector<int32_t> t_name, t_cut, t_count;
+    std::vector<int64_t> t_pos;
+    std::string text;                   // conseq_ins.csv, formatted on first use
+    bool text_valid = false;
+    int32_t *d_list = nullptr, *d_res = nullptr, *d_rref = nullptr, *d_tcnt = nullptr, *d_trep = nullptr,
+            *d_uniq = nullptr, *d_ctr = nullptr;
+    int64_t *d_recoff = nullptr, *d_byteoff = nullptr, *d_slot = nullptr, *d_goff = nullptr;
+    S2AInsRec *d_rec = nullptr;
+    uint64_t *d_h = nullptr, *d_tkey = nullptr;
+    uint8_t *d_out = nullptr, *d_gather = nullptr;
+};
+
 struct S2AState {
     // ---- rows of the last remap.csv (host) ----
     int64_t n_rows = 0;
@@ -127,6 +156,7 @@ struct S2AState {
     // ---- host timings of the last call (ms) ----
     double t_parse = 0, t_device = 0, t_format[3] = {0, 0, 0};
     S2AClip clip;
+    S2AIns ins;
     // ---- this rank's part of a sharded sam2aln ----
     S2AShard *shard = nullptr;
     ~S2AState() { if (shard) s2a_shard_free(shard); }
@@ -154,6 +184,7 @@ inline void s2a_begin(Ctx &c, S2AState &S)
     S.res.clear();
     S.clip.state = CLIP_NONE;
     S.clip.text_valid = false;
+    S.ins.done = S.ins.text_valid = false;
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
     S.out_valid = 0;
 }
@@ -177,6 +208,9 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev = null
 // k_s2a_clip and k_s2a_clip_scan over the units of the last s2a_run, once per
 // call: S.clip's (name, pos, count) lists
 int s2a_clip_run(Ctx &c, S2AState &S);
+// k_s2a_ins_rec, k_s2a_ins_merge and the grouping over the units of the last
+// s2a_run that hold an I op, once per call: S.ins's rows and totals
+int s2a_ins_run(Ctx &c, S2AState &S);
 // Units, failure causes, group names and QNAMEs of the resident rows (one
 // per read, in read order) instead of s2a_parse: S.pos, S.flag, S.n_cig,
 // S.cig_off and S.cig hold the rows as k_s2a_stage wrote them; sam_ref[r]

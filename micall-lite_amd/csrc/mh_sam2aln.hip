@@ -25,6 +25,11 @@
 //   k_s2a_clip, k_s2a_clip_scan   only when mh_sam2aln_clipping asks: the
 //                 positions each merged unit soft-clips and no mate aligns,
 //                 counted per reference (clipping.csv; no reference code)
+//   k_s2a_ins_rec, k_s2a_ins_merge, k_s2a_ins_tab   only when
+//                 mh_sam2aln_conseq_ins asks: the mates' insertions keyed by
+//                 consensus position, merged as merge_inserts does
+//                 (sam2aln.py:240-273) and counted per distinct string
+//                 (conseq_ins.csv)
 // Bit-for-bit specification: the reference itself (tests/golden/e2e/*/aligned.csv
 // etc. were produced by running micall.core.sam2aln on the same remap.csv).
 #include <fcntl.h>
@@ -37,6 +42,7 @@
 #include <chrono>
 #include <cstring>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <vector>
 
@@ -68,6 +74,17 @@ static void s2a_free_device(S2AState &S)
     K.d_lo = K.d_base = nullptr;
     K.d_wlen = K.d_diff = K.d_idx = K.d_cnt = K.d_n = nullptr;
     K.state = CLIP_NONE;
+    S2AIns &I = S.ins;
+    hipFree(I.d_list); hipFree(I.d_res); hipFree(I.d_rref); hipFree(I.d_tcnt); hipFree(I.d_trep);
+    hipFree(I.d_uniq); hipFree(I.d_ctr); hipFree(I.d_recoff); hipFree(I.d_byteoff); hipFree(I.d_slot);
+    hipFree(I.d_goff); hipFree(I.d_rec); hipFree(I.d_h); hipFree(I.d_tkey); hipFree(I.d_out);
+    hipFree(I.d_gather);
+    I.d_list = I.d_res = I.d_rref = I.d_tcnt = I.d_trep = I.d_uniq = I.d_ctr = nullptr;
+    I.d_recoff = I.d_byteoff = I.d_slot = I.d_goff = nullptr;
+    I.d_rec = nullptr;
+    I.d_h = I.d_tkey = nullptr;
+    I.d_out = I.d_gather = nullptr;
+    I.done = false;
     S.dcap.clear();
 }
 
@@ -1127,6 +1144,566 @@ static int s2a_clip_of(mh_ctx *ctx, const char *what, bool text, S2AState **out)
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Merged insertions (conseq_ins.csv; DESIGN.md section 6, "Merged
+// insertions").  Per read, walking the CIGAR with ref = POS - 1 and left = 0:
+// an I op of n > 0 bytes is the insertion (seq, qual)[left, left + n) at key
+// ref, the last I op of a key standing for it.  A unit's keys are the union
+// of its mates'; per cutoff the string of a key is merge_inserts'
+// (sam2aln.py:240-273), and a unit counts at the cutoffs whose merge entry is
+// S2A_OK.
+//
+// k_s2a_ins_rec    one wave per listed unit (the host lists the units with an
+//                  I op): the ops of each mate over the lanes, ref / left by
+//                  s2a_scan, the I ops compacted into a per-mate LDS list
+//                  (keys never decrease along a read, so equal keys are
+//                  neighbours and the last of a run stands).  One record slot
+//                  per list element: mate 1's standing elements with mate 2's
+//                  partner (binary search), then mate 2's without a partner;
+//                  the others stay unused (both lengths 0).  The merged bytes
+//                  of a unit's records are placed by a scan of max(len1, len2).
+// k_s2a_ins_merge  one wave per record, every cutoff at once: min(qual) of
+//                  each mate by wave reduction, merge_pairs' (character,
+//                  threshold) once per position, and per kept cutoff the
+//                  bytes into the entry's slot and two position-keyed sums
+//                  mixed with (reference, cutoff, key, length).
+// k_s2a_ins_tab    a thread per entry into the table (table_claim), equal
+//                  keys of a wave combined first.
+// k_s2a_verify, k_s2a_compact and k_s2a_gather then run unchanged on the
+// entries: res = (status, key, length, 0) per entry, rref per record.
+// ---------------------------------------------------------------------------
+struct InsRecArgs {
+    const int64_t *soff;
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int64_t *units;
+    const int32_t *list;      // merge units with an I op
+    const int64_t *rec_off;   // per listed unit (+ end): its first record slot
+    const int64_t *byte_off;  // per listed unit: its first merged byte
+    int64_t n_list;
+    int icap, wave_bytes;     // I ops of one read at most; LDS bytes of a wave
+    S2AInsRec *rec;
+};
+
+// the I ops (n > 0) of row r into key / left / len, in op order; their number
+__device__ __forceinline__ int ins_ops(const InsRecArgs &A, int64_t r, int lane, int32_t *key,
+                                       int32_t *left, int32_t *len)
+{
+    const int nc = A.n_cig[r];
+    const uint32_t *ops = A.cig + A.cig_off[r];
+    int rf0 = A.pos[r] - 1, rd0 = 0, cnt = 0;
+    for (int o0 = 0; o0 < nc; o0 += 64) {
+        const int o = o0 + lane;
+        int dref = 0, dread = 0, n = 0, isi = 0;
+        if (o < nc) {
+            const uint32_t op = ops[o];
+            const int t = (int)(op & 15);
+            n = (int)(op >> 4);
+            if (t == MH_OP_M) { dref = n; dread = n; }
+            else if (t == MH_OP_D) dref = n;
+            else dread = n;                              // I, S (checked on the host)
+            isi = t == MH_OP_I && n > 0;
+        }
+        const int iref = s2a_scan(dref, lane), iread = s2a_scan(dread, lane), ii = s2a_scan(isi, lane);
+        const int j = cnt + ii - 1;
+        if (isi && j < A.icap) {
+            key[j] = rf0 + iref - dref;
+            left[j] = rd0 + iread - dread;
+            len[j] = n;
+        }
+        rf0 += __shfl(iref, 63, 64);
+        rd0 += __shfl(iread, 63, 64);
+        cnt += __shfl(ii, 63, 64);
+    }
+    return cnt < A.icap ? cnt : A.icap;
+}
+
+// the last element of the sorted key[0, n) that equals k, -1 for none
+__device__ __forceinline__ int ins_find(const int32_t *key, int n, int k)
+{
+    int lo = 0, hi = n;                                  // first element > k
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key[mid] <= k) lo = mid + 1; else hi = mid;
+    }
+    return lo > 0 && key[lo - 1] == k ? lo - 1 : -1;
+}
+
+__global__ __launch_bounds__(256) void k_s2a_ins_rec(InsRecArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wpb = blockDim.x >> 6;
+    int32_t *wb = (int32_t *)(smem + (size_t)wv * A.wave_bytes);
+    int32_t *key1 = wb, *left1 = wb + A.icap, *len1 = wb + 2 * A.icap;
+    int32_t *key2 = wb + 3 * A.icap, *left2 = wb + 4 * A.icap, *len2 = wb + 5 * A.icap;
+    for (int64_t i = (int64_t)blockIdx.x * wpb + wv; i < A.n_list; i += (int64_t)gridDim.x * wpb) {
+        const int m = A.list[i];
+        const int64_t r1 = A.units[2 * (int64_t)m], r2 = A.units[2 * (int64_t)m + 1];
+        const int n1 = ins_ops(A, r1, lane, key1, left1, len1);
+        const int n2 = r2 >= 0 ? ins_ops(A, r2, lane, key2, left2, len2) : 0;
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const int64_t s1 = A.soff[r1], s2 = r2 >= 0 ? A.soff[r2] : 0;
+        const int64_t rec0 = A.rec_off[i];
+        // the host counted the same I ops: never more slots than it reserved
+        int nslot = (int)(A.rec_off[i + 1] - rec0);
+        if (nslot > n1 + n2) nslot = n1 + n2;
+        int64_t bytes = A.byte_off[i];
+        for (int j0 = 0; j0 < nslot; j0 += 64) {
+            const int j = j0 + lane;
+            S2AInsRec R{m, 0, 0, 0, 0, 0, 0};
+            if (j < n1) {
+                if (j + 1 >= n1 || key1[j + 1] != key1[j]) {
+                    R.key = key1[j];
+                    R.len1 = len1[j];
+                    R.src1 = s1 + left1[j];
+                    const int p = ins_find(key2, n2, R.key);
+                    if (p >= 0) { R.len2 = len2[p]; R.src2 = s2 + left2[p]; }
+                }
+            } else if (j < nslot) {
+                const int t = j - n1;
+                if ((t + 1 >= n2 || key2[t + 1] != key2[t]) && ins_find(key1, n1, key2[t]) < 0) {
+                    R.key = key2[t];
+                    R.len2 = len2[t];
+                    R.src2 = s2 + left2[t];
+                }
+            }
+            const int L = R.len1 > R.len2 ? R.len1 : R.len2;
+            const int run = s2a_scan(L, lane);
+            R.boff = bytes + run - L;
+            if (j < nslot) A.rec[rec0 + j] = R;
+            bytes += __shfl(run, 63, 64);
+        }
+        // slots past the I ops found (none, unless the host's count differs)
+        for (int64_t j = rec0 + nslot + lane; j < A.rec_off[i + 1]; j += 64)
+            A.rec[j] = S2AInsRec{m, 0, 0, 0, 0, 0, 0};
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+struct InsMergeArgs {
+    const uint8_t *seq, *qual;
+    const S2AInsRec *rec;
+    int64_t n_rec;
+    int n_cut;
+    unsigned char cut[S2A_MAX_CUTS];
+    const int32_t *mres;      // the merge's res: 4 per (unit, cutoff)
+    const int32_t *uref;
+    uint8_t *out;
+    int32_t *res;             // 4 per entry: status, key, length, 0
+    int32_t *rref;            // per record: its reference
+    int64_t *slot;            // per entry: its bytes in out
+    uint64_t *h;              // 2 per entry
+    int32_t *ctr;             // [2]: the least unit with a '-' among its inserted bytes
+};
+
+constexpr int S2A_INS_SKIP = -1;   // status of an entry that is no row
+
+template <int NC>
+__global__ __launch_bounds__(256) void k_s2a_ins_merge(InsMergeArgs A)
+{
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const int n_cut = NC == 1 ? 1 : A.n_cut;
+    unsigned char cut[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) cut[k] = A.cut[k];
+    for (int64_t r = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); r < A.n_rec;
+         r += (int64_t)gridDim.x * wpb) {
+        const S2AInsRec R = A.rec[r];
+        const int64_t e0 = r * n_cut;
+        const int L = R.len1 > R.len2 ? R.len1 : R.len2;
+        // ---- min(qual) of each mate's insertion; a '-' is refused ----
+        int min1 = 256, min2 = 256, dash = 0;
+        for (int j = lane; j < R.len1; j += 64) {
+            min1 = min(min1, (int)A.qual[R.src1 + j]);
+            dash |= A.seq[R.src1 + j] == '-';
+        }
+        for (int j = lane; j < R.len2; j += 64) {
+            min2 = min(min2, (int)A.qual[R.src2 + j]);
+            dash |= A.seq[R.src2 + j] == '-';
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            min1 = min(min1, __shfl_xor(min1, o, 64));
+            min2 = min(min2, __shfl_xor(min2, o, 64));
+        }
+        const bool refused = __any(dash);
+        if (refused && lane == 0) atomicMin(&A.ctr[2], R.unit);
+        // ---- merge_pairs' roles: seq1 = a is the shorter string, mate 1 on a tie ----
+        const bool swap = R.len1 > R.len2;
+        const int64_t sa = swap ? R.src2 : R.src1, sb = swap ? R.src1 : R.src2;
+        const int la = swap ? R.len2 : R.len1;
+        // per cutoff: 0 no row, 1 mate 1's string alone, 2 the merged string
+        int mode[NC], elen[NC];
+        int64_t slot[NC];
+        uint64_t h1[NC], h2[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            mode[k] = 0;
+            if (k < n_cut && L > 0 && !refused &&
+                A.mres[4 * ((int64_t)R.unit * n_cut + k)] == S2A_OK) {
+                if (R.len2 > 0 && min2 > (int)cut[k]) mode[k] = 2;
+                else if (R.len1 > 0 && min1 > (int)cut[k]) mode[k] = 1;
+            }
+            elen[k] = mode[k] == 2 ? L : mode[k] == 1 ? R.len1 : 0;
+            slot[k] = (int64_t)n_cut * R.boff + (int64_t)k * L;
+            h1[k] = h2[k] = 0;
+        }
+        for (int j = lane; j < L; j += 64) {
+            char ch = 0, c1 = 0;
+            unsigned char thr = S2A_ALWAYS;
+            if (R.len2 > 0) {                            // (ch, thr) as in s2a_pos, no gaps
+                ch = (char)A.seq[sb + j];
+                thr = A.qual[sb + j];
+                if (j < la) {
+                    const char ca = (char)A.seq[sa + j];
+                    const unsigned char qa = A.qual[sa + j];
+                    if (ca == ch) {
+                        thr = qa > thr ? qa : thr;
+                    } else {
+                        const int dq = (int)thr - (int)qa;
+                        if (dq <= -5) { ch = ca; thr = qa; }
+                        else if (dq < 5) { ch = 'N'; thr = S2A_ALWAYS; }
+                    }
+                }
+            }
+            if (j < R.len1) c1 = (char)A.seq[R.src1 + j];
+            const uint64_t k1 = mix64(2ull * (uint64_t)j + 1ull) | 1ull;
+            const uint64_t k2 = mix64((uint64_t)j ^ 0x5bd1e995ull << 32) | 1ull;
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                if (j < elen[k]) {
+                    const char mch = mode[k] == 2 ? (thr > cut[k] ? ch : 'N') : c1;
+                    A.out[slot[k] + j] = (uint8_t)mch;
+                    h1[k] += k1 * (uint64_t)(uint8_t)mch;
+                    h2[k] += k2 * (uint64_t)(uint8_t)mch;
+                }
+            }
+        }
+        const int ref = A.uref[R.unit];
+        if (lane == 0) A.rref[r] = ref;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            if (k >= n_cut) break;
+            for (int o = 32; o > 0; o >>= 1) {
+                h1[k] += __shfl_xor(h1[k], o, 64);
+                h2[k] += __shfl_xor(h2[k], o, 64);
+            }
+            const uint64_t grp = (uint64_t)(uint32_t)ref * (uint64_t)n_cut + (uint64_t)k;
+            const uint64_t meta = mix64(grp) ^ ((uint64_t)(uint32_t)R.key << 32) ^
+                                  (uint64_t)(uint32_t)elen[k];
+            h1[k] = mix64(h1[k] ^ mix64(meta));
+            h2[k] = mix64(h2[k] + 0x2545f4914f6cdd1dull * mix64(meta + 7));
+            if (lane == 0) {
+                const int64_t e = e0 + k;
+                A.res[4 * e] = mode[k] ? S2A_OK : S2A_INS_SKIP;
+                A.res[4 * e + 1] = R.key;
+                A.res[4 * e + 2] = elen[k];
+                A.res[4 * e + 3] = 0;
+                A.slot[e] = slot[k];
+                A.h[2 * e] = h1[k];
+                A.h[2 * e + 1] = h2[k];
+            }
+        }
+    }
+}
+
+// A thread per entry.  An amplicon puts most of a wave's entries on one
+// (position, string), and atomics on one address serialise: for
+// INS_COMBINE rounds the lanes that hold the lowest active lane's key are
+// counted by a ballot and that lane alone goes to the table (entries rise
+// with the lane, so it is also the least of them); what is left goes lane by
+// lane.  combine 0: every entry on its own (measurements).
+constexpr int INS_COMBINE = 4;
+
+__global__ __launch_bounds__(256) void k_s2a_ins_tab(const int32_t *res, const uint64_t *h, int64_t n,
+                                                     uint64_t *tkey, int32_t *tcnt, int32_t *trep,
+                                                     uint64_t mask, int combine)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t key = 0;
+    bool todo = false;
+    if (e < n && res[4 * e] == S2A_OK) { key = s2a_key(h[2 * e]); todo = true; }
+    for (int round = 0; combine && round < INS_COMBINE; ++round) {
+        const unsigned long long act = __ballot(todo);
+        if (!act) break;
+        const int leader = __ffsll((long long)act) - 1;
+        const uint64_t k = __shfl((unsigned long long)key, leader, 64);
+        const bool mine = todo && key == k;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) {
+            const uint64_t s = table_claim(tkey, mask, key & mask, key).slot;
+            atomicAdd(&tcnt[s], (int32_t)__popcll(same));
+            atomicMin(&trep[s], (int32_t)e);
+        }
+        todo = todo && !mine;
+    }
+    if (todo) {
+        const uint64_t s = table_claim(tkey, mask, key & mask, key).slot;
+        atomicAdd(&tcnt[s], 1);
+        atomicMin(&trep[s], (int32_t)e);
+    }
+}
+
+static void s2a_ins_clear(S2AIns &I)
+{
+    I.done = I.text_valid = false;
+    I.name.clear(); I.cut.clear(); I.count.clear(); I.pos.clear(); I.soff.assign(1, 0);
+    I.strings.clear();
+    I.t_name.clear(); I.t_cut.clear(); I.t_count.clear(); I.t_pos.clear();
+}
+
+int s2a_ins_run(Ctx &c, S2AState &S)
+{
+    S2AIns &I = S.ins;
+    if (I.done) return 0;
+    if (S.clip.state == CLIP_NONE) {
+        set_error("sam2aln conseq_ins: no rows of a sam2aln call are on the device");
+        return -3;
+    }
+    const S2ADevRows &rows = S.clip.rows;
+    if (S.n_merge && rows.cig != S.d_cig && (!c.map.valid || rows.cig != c.map.pool)) {
+        set_error("sam2aln conseq_ins: the mapping pass the rows came from is gone");
+        return -3;
+    }
+    if (S.n_merge && rows.soff != S.d_soff && (rows.soff != c.reads.off || S.staged_reads != c.reads.n)) {
+        set_error("sam2aln conseq_ins: the resident reads the rows came from are gone");
+        return -3;
+    }
+    s2a_ins_clear(I);
+    const int nc = (int)S.q_cutoffs.size();
+    const int64_t nu = (int64_t)S.u1.size();
+    // ---- the units with an I op, their record slots (one per I op) and
+    // merged bytes (the I ops' lengths: at least the sum of max(len1, len2)) ----
+    std::vector<int32_t> list;
+    std::vector<int64_t> list_unit, rec_off(1, 0), byte_off(1, 0);
+    int icap = 1;
+    for (int64_t u = 0; S.n_merge && u < nu; ++u) {
+        if (S.ucause[u] >= 0) continue;
+        int64_t nrec = 0, nbytes = 0;
+        for (int64_t r : {S.u1[u], S.upaired[u] ? S.u2[u] : (int64_t)-1}) {
+            if (r < 0) continue;
+            int ni = 0;
+            for (int o = 0; o < S.n_cig[r]; ++o) {
+                const uint32_t op = S.cig[S.cig_off[r] + o];
+                if ((op & 15) == MH_OP_I && (op >> 4) > 0) { ++ni; nbytes += op >> 4; }
+            }
+            icap = std::max(icap, ni);
+            nrec += ni;
+        }
+        if (!nrec) continue;
+        list.push_back((int32_t)S.merge_of_unit[u]);
+        list_unit.push_back(u);
+        rec_off.push_back(rec_off.back() + nrec);
+        byte_off.push_back(byte_off.back() + nbytes);
+    }
+    const int64_t nl = (int64_t)list.size(), nrec = rec_off.back(), ne = nrec * nc;
+    const int64_t nbytes = byte_off.back() * nc;
+    if (nl == 0) { I.done = true; return 0; }
+    if (ne > 0x7f7f7f7f) {               // entries are int32 in the table and in uniq
+        set_error("sam2aln conseq_ins: %lld insertions at %d q-cutoffs are too many entries",
+                  (long long)nrec, nc);
+        return -3;
+    }
+    const int wave_bytes = (6 * 4 * icap + 15) & ~15;
+    int wpb = 4;
+    while (wpb > 1 && (size_t)wpb * wave_bytes > 64 * 1024) --wpb;
+    if ((size_t)wave_bytes > 160 * 1024) {
+        set_error("sam2aln conseq_ins: a read with %d insertions is too many for LDS", icap);
+        return -3;
+    }
+    hipStream_t s = c.stream;
+    if (int st = s2a_upload(S, I.d_list, list, s)) return st;
+    if (int st = s2a_upload(S, I.d_recoff, rec_off, s)) return st;
+    if (int st = s2a_upload(S, I.d_byteoff, byte_off, s)) return st;
+    uint64_t tsize = 1024;
+    while (tsize < (uint64_t)(2 * ne)) tsize <<= 1;
+    if (int st = dev_reserve(S, I.d_rec, sizeof(S2AInsRec) * (size_t)nrec)) return st;
+    if (int st = dev_reserve(S, I.d_rref, sizeof(int32_t) * (size_t)nrec)) return st;
+    if (int st = dev_reserve(S, I.d_out, (size_t)nbytes)) return st;
+    if (int st = dev_reserve(S, I.d_res, sizeof(int32_t) * 4 * (size_t)ne)) return st;
+    if (int st = dev_reserve(S, I.d_slot, sizeof(int64_t) * (size_t)ne)) return st;
+    if (int st = dev_reserve(S, I.d_h, sizeof(uint64_t) * 2 * (size_t)ne)) return st;
+    if (int st = dev_reserve(S, I.d_ctr, sizeof(int32_t) * 4)) return st;
+    if (int st = dev_reserve(S, I.d_tkey, sizeof(uint64_t) * tsize)) return st;
+    if (int st = dev_reserve(S, I.d_tcnt, sizeof(int32_t) * tsize)) return st;
+    if (int st = dev_reserve(S, I.d_trep, sizeof(int32_t) * tsize)) return st;
+    if (int st = dev_reserve(S, I.d_uniq, sizeof(int32_t) * 2 * (size_t)ne)) return st;
+    static const int32_t ctr0[4] = {0, 0, INT32_MAX, 0};
+    MH_HIP(hipMemcpyAsync(I.d_ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
+    MH_HIP(hipMemsetAsync(I.d_tkey, 0, sizeof(uint64_t) * tsize, s));
+    MH_HIP(hipMemsetAsync(I.d_tcnt, 0, sizeof(int32_t) * tsize, s));
+    MH_HIP(hipMemsetAsync(I.d_trep, 0x7f, sizeof(int32_t) * tsize, s));
+
+    InsRecArgs ra{rows.soff, rows.pos, rows.cig_off, rows.n_cig, rows.cig, S.d_units, I.d_list,
+                  I.d_recoff, I.d_byteoff, nl, icap, wave_bytes, I.d_rec};
+    int64_t rb = (nl + wpb - 1) / wpb;
+    if (rb > 256 * 64) rb = 256 * 64;
+    MH_HIP(hipFuncSetAttribute((const void *)k_s2a_ins_rec, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               wpb * wave_bytes));
+    const int p0 = prof_begin(c, "k_s2a_ins_rec");
+    hipLaunchKernelGGL(k_s2a_ins_rec, dim3((unsigned)rb), dim3(64 * wpb), wpb * wave_bytes, s, ra);
+    prof_end(c, p0);
+    MH_HIP(hipGetLastError());
+    InsMergeArgs ma{rows.seq, rows.qual, I.d_rec, nrec, nc, {}, S.d_res, S.d_uref, I.d_out, I.d_res,
+                    I.d_rref, I.d_slot, I.d_h, I.d_ctr};
+    for (int k = 0; k < nc; ++k) ma.cut[k] = (unsigned char)(S.q_cutoffs[k] + 33);
+    void (*merge)(InsMergeArgs) = nc == 1 ? k_s2a_ins_merge<1> : nc == 2 ? k_s2a_ins_merge<2>
+                                  : nc <= 4 ? k_s2a_ins_merge<4> : k_s2a_ins_merge<8>;
+    int64_t mb = (nrec + 3) / 4;
+    if (mb > 256 * 64) mb = 256 * 64;
+    const int p1 = prof_begin(c, "k_s2a_ins_merge");
+    hipLaunchKernelGGL(merge, dim3((unsigned)mb), dim3(256), 0, s, ma);
+    prof_end(c, p1);
+    MH_HIP(hipGetLastError());
+    static const bool combine = !(getenv("MICALL_INS_COMBINE") && *getenv("MICALL_INS_COMBINE") == '0');
+    const int64_t tb = (ne + 255) / 256;     // a thread per entry: ne <= 0x7f7f7f7f
+    const int p2 = prof_begin(c, "k_s2a_ins_tab");
+    hipLaunchKernelGGL(k_s2a_ins_tab, dim3((unsigned)tb), dim3(256), 0, s, I.d_res, I.d_h, ne, I.d_tkey,
+                       I.d_tcnt, I.d_trep, tsize - 1, combine ? 1 : 0);
+    prof_end(c, p2);
+    MH_HIP(hipGetLastError());
+    int64_t vb = (ne + 3) / 4;
+    if (vb > 256 * 64) vb = 256 * 64;
+    const int p3 = prof_begin(c, "k_s2a_ins_group");
+    hipLaunchKernelGGL(k_s2a_verify, dim3((unsigned)vb), dim3(256), 0, s, I.d_res, I.d_h, I.d_rref,
+                       I.d_slot, I.d_out, ne, nc, I.d_tkey, I.d_trep, tsize - 1, I.d_ctr);
+    int64_t cb = (int64_t)((tsize + 255) / 256);
+    if (cb > 65536) cb = 65536;
+    hipLaunchKernelGGL(k_s2a_compact, dim3((unsigned)cb), dim3(256), 0, s, I.d_tkey, I.d_tcnt, I.d_trep,
+                       tsize, I.d_uniq, I.d_ctr);
+    prof_end(c, p3);
+    MH_HIP(hipGetLastError());
+    int32_t ctr[4];
+    MH_HIP(hipMemcpyAsync(ctr, I.d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    prof_flush(c);
+    if (ctr[2] != INT32_MAX) {
+        int64_t u = -1;
+        for (int64_t k = 0; k < nl; ++k)
+            if (list[k] == ctr[2]) u = list_unit[k];
+        const int64_t r = u >= 0 ? S.u1[u] : -1;
+        set_error("sam2aln conseq_ins: read %.*s has a '-' among its inserted bases",
+                  r >= 0 ? (int)S.qlen[r] : 1, r >= 0 ? S.qpool.data() + S.qoff[r] : "?");
+        return -3;
+    }
+    if (ctr[0]) {
+        set_error("sam2aln conseq_ins: insertion hash collision (distinct insertions share a key)");
+        return -4;
+    }
+    const int64_t nq = ctr[1];
+    if (nq < 0 || nq > ne) {
+        set_error("sam2aln conseq_ins: %lld distinct insertions of %lld entries", (long long)nq, (long long)ne);
+        return -4;
+    }
+    if (nq == 0) { I.done = true; return 0; }
+    std::vector<int32_t> uniq(2 * (size_t)nq), res(4 * (size_t)ne), rref((size_t)nrec);
+    MH_HIP(hipMemcpyAsync(uniq.data(), I.d_uniq, sizeof(int32_t) * uniq.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(res.data(), I.d_res, sizeof(int32_t) * res.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(rref.data(), I.d_rref, sizeof(int32_t) * rref.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    std::vector<int64_t> goff((size_t)nq + 1, 0);
+    for (int64_t k = 0; k < nq; ++k) {
+        const int64_t e = uniq[2 * k];
+        if (e < 0 || e >= ne || res[4 * e] != S2A_OK || res[4 * e + 2] <= 0) {
+            set_error("sam2aln conseq_ins: distinct insertion %lld names no entry", (long long)k);
+            return -4;
+        }
+        goff[k + 1] = goff[k] + res[4 * e + 2];
+    }
+    std::string bytes((size_t)goff[nq], '\0');
+    if (int st = s2a_upload(S, I.d_goff, goff, s)) return st;
+    if (int st = dev_reserve(S, I.d_gather, bytes.size())) return st;
+    int64_t gb = (nq + 3) / 4;
+    if (gb > 256 * 64) gb = 256 * 64;
+    hipLaunchKernelGGL(k_s2a_gather, dim3((unsigned)gb), dim3(256), 0, s, I.d_uniq, I.d_goff, I.d_res,
+                       I.d_slot, I.d_out, nq, I.d_gather);
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipMemcpyAsync(&bytes[0], I.d_gather, bytes.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    // ---- file order: references as Python sorts str, cutoff, position,
+    // count descending, string as bytes ----
+    std::vector<int64_t> order((size_t)nq);
+    for (int64_t k = 0; k < nq; ++k) order[k] = k;
+    auto name_of = [&](int64_t k) -> const std::string & { return S.names[rref[uniq[2 * k] / nc]]; };
+    auto str_of = [&](int64_t k) {
+        return std::string_view(bytes.data() + goff[k], (size_t)(goff[k + 1] - goff[k]));
+    };
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+        const int64_t ex = uniq[2 * x], ey = uniq[2 * y];
+        if (const int d = name_of(x).compare(name_of(y))) return d < 0;
+        const int qx = S.q_cutoffs[ex % nc], qy = S.q_cutoffs[ey % nc];
+        if (qx != qy) return qx < qy;
+        if (res[4 * ex + 1] != res[4 * ey + 1]) return res[4 * ex + 1] < res[4 * ey + 1];
+        if (uniq[2 * x + 1] != uniq[2 * y + 1]) return uniq[2 * x + 1] > uniq[2 * y + 1];
+        return str_of(x) < str_of(y);
+    });
+    for (int64_t k : order) {
+        const int64_t e = uniq[2 * k];
+        I.name.push_back(rref[e / nc]);
+        I.cut.push_back((int32_t)(e % nc));
+        I.pos.push_back(res[4 * e + 1]);
+        I.count.push_back(uniq[2 * k + 1]);
+        I.strings.append(str_of(k));
+        I.soff.push_back((int64_t)I.strings.size());
+        if (!I.t_name.empty() && I.t_name.back() == I.name.back() && I.t_cut.back() == I.cut.back() &&
+            I.t_pos.back() == I.pos.back()) {
+            I.t_count.back() += I.count.back();
+        } else {
+            I.t_name.push_back(I.name.back());
+            I.t_cut.push_back(I.cut.back());
+            I.t_pos.push_back(I.pos.back());
+            I.t_count.push_back(I.count.back());
+        }
+    }
+    I.done = true;
+    return 0;
+}
+
+// conseq_ins.csv of S.ins's rows: refname,qcut,pos,insert,count
+static void s2a_ins_text(S2AState &S)
+{
+    S2AIns &I = S.ins;
+    if (I.text_valid) return;
+    std::string &o = I.text;
+    o.assign("refname,qcut,pos,insert,count\n");
+    for (size_t j = 0; j < I.name.size(); ++j) {
+        const std::string &rn = S.names[I.name[j]];
+        csv_field(o, rn.data(), rn.size());
+        o.push_back(',');
+        o += std::to_string(S.q_cutoffs[I.cut[j]]);
+        o.push_back(',');
+        o += std::to_string((long long)I.pos[j]);
+        o.push_back(',');
+        csv_field(o, I.strings.data() + I.soff[j], (size_t)(I.soff[j + 1] - I.soff[j]));
+        o.push_back(',');
+        o += std::to_string(I.count[j]);
+        o.push_back('\n');
+    }
+    I.text_valid = true;
+}
+
+// the insertions of the context's last sam2aln call, counted now if not yet
+static int s2a_ins_of(mh_ctx *ctx, const char *what, bool text, S2AState **out)
+{
+    Ctx &c = *ctx_of(ctx);
+    if (!c.s2a) { set_error("%s: no sam2aln results", what); return -3; }
+    MH_HIP(hipSetDevice(c.device));
+    try {
+        if (int st = s2a_ins_run(c, *c.s2a)) return st;
+        if (text) s2a_ins_text(*c.s2a);
+    } catch (const std::exception &e) {
+        c.s2a->ins.done = c.s2a->ins.text_valid = false;
+        set_error("%s: out of memory (%s)", what, e.what());
+        return -2;
+    }
+    *out = c.s2a;
+    return 0;
+}
+
 }  // namespace mh
 
 using namespace mh;
@@ -1498,6 +2075,52 @@ extern "C" int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *po
         memcpy(name_id, K.name.data(), sizeof(int32_t) * K.name.size());
         memcpy(pos, K.pos.data(), sizeof(int64_t) * K.pos.size());
         memcpy(count, K.count.data(), sizeof(int32_t) * K.count.size());
+    }
+    return 0;
+}
+
+extern "C" int mh_sam2aln_conseq_ins(mh_ctx *ctx, char *buf, size_t cap, size_t *used)
+{
+    if (!ctx || !used) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_ins_of(ctx, "mh_sam2aln_conseq_ins", true, &S)) return st;
+    const std::string &t = S->ins.text;
+    *used = t.size();
+    if (!buf) return 0;
+    if (cap < t.size()) { set_error("mh_sam2aln_conseq_ins: buffer too small"); return -2; }
+    memcpy(buf, t.data(), t.size());
+    return 0;
+}
+
+extern "C" int mh_sam2aln_conseq_ins_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written)
+{
+    if (!ctx || fd < 0 || offset < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_ins_of(ctx, "mh_sam2aln_conseq_ins_write", true, &S)) return st;
+    const std::string &t = S->ins.text;
+    if (const int e = write_all_at(fd, t.data(), t.size(), offset)) {
+        set_error("mh_sam2aln_conseq_ins_write: write failed (%s)", strerror(e));
+        return -4;
+    }
+    if (written) *written = (int64_t)t.size();
+    return 0;
+}
+
+extern "C" int mh_sam2aln_ins_counts(mh_ctx *ctx, int32_t *name_id, int32_t *cut_index, int64_t *pos,
+                                     int32_t *count, int64_t cap, int64_t *n)
+{
+    if (!ctx || !n || cap < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_ins_of(ctx, "mh_sam2aln_ins_counts", false, &S)) return st;
+    const S2AIns &I = S->ins;
+    *n = (int64_t)I.t_name.size();
+    if (!name_id || !cut_index || !pos || !count) return 0;
+    if (cap < *n) { set_error("mh_sam2aln_ins_counts: buffer too small"); return -2; }
+    if (*n) {
+        memcpy(name_id, I.t_name.data(), sizeof(int32_t) * I.t_name.size());
+        memcpy(cut_index, I.t_cut.data(), sizeof(int32_t) * I.t_cut.size());
+        memcpy(pos, I.t_pos.data(), sizeof(int64_t) * I.t_pos.size());
+        memcpy(count, I.t_count.data(), sizeof(int32_t) * I.t_count.size());
     }
     return 0;
 }

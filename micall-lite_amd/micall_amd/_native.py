@@ -149,6 +149,10 @@ def _declare(L):
                                  ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_clipping_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_clip_counts': ([_P, _P, _P, _P, ctypes.c_int64, _I64P], ctypes.c_int),
+        'mh_sam2aln_conseq_ins': ([_P, ctypes.c_char_p, ctypes.c_size_t,
+                                   ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_sam2aln_conseq_ins_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
+        'mh_sam2aln_ins_counts': ([_P, _P, _P, _P, _P, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_written': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), _I64P], ctypes.c_int),
         'mh_sam2aln_serial': ([_P, _I64P], ctypes.c_int),
         'mh_a2c_load_resident': ([_P, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
@@ -687,6 +691,46 @@ class Context:
             check(lib().mh_sam2aln_clip_counts(self.h, _ptr(ids), _ptr(pos), _ptr(cnt), n.value,
                                                ctypes.byref(n)), 'mh_sam2aln_clip_counts')
         return ids, pos, cnt
+
+    def sam2aln_conseq_ins(self):
+        """conseq_ins.csv text of the last sam2aln call (mh_sam2aln_conseq_ins):
+        per reference, q-cutoff, consensus position and merged string the
+        units that carry the insertion.  The device pass runs on the first
+        request."""
+        used = ctypes.c_size_t()
+        check(lib().mh_sam2aln_conseq_ins(self.h, None, 0, ctypes.byref(used)), 'mh_sam2aln_conseq_ins')
+        buf = bytearray(used.value)
+        cbuf = (ctypes.c_char * len(buf)).from_buffer(buf)
+        check(lib().mh_sam2aln_conseq_ins(self.h, cbuf, len(buf), ctypes.byref(used)),
+              'mh_sam2aln_conseq_ins')
+        del cbuf
+        return buf.decode()
+
+    def sam2aln_conseq_ins_write(self, fd, offset):
+        """conseq_ins.csv written to fd at offset (pwrite); bytes written."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_conseq_ins_write(self.h, int(fd), int(offset), ctypes.byref(n)),
+              'mh_sam2aln_conseq_ins_write')
+        return n.value
+
+    def sam2aln_ins_counts(self):
+        """(name ids int32, cutoff indexes int32, positions int64, counts
+        int32): conseq_ins.csv's counts summed over the strings of each
+        (reference, cutoff, position), in the text's order
+        (mh_sam2aln_ins_counts); a name id indexes the call's reference names
+        in first-seen order (sam2aln_part_names), a cutoff index its
+        q-cutoffs as given."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_ins_counts(self.h, None, None, None, None, 0, ctypes.byref(n)),
+              'mh_sam2aln_ins_counts')
+        ids = np.empty(n.value, dtype=np.int32)
+        cut = np.empty(n.value, dtype=np.int32)
+        pos = np.empty(n.value, dtype=np.int64)
+        cnt = np.empty(n.value, dtype=np.int32)
+        if n.value:
+            check(lib().mh_sam2aln_ins_counts(self.h, _ptr(ids), _ptr(cut), _ptr(pos), _ptr(cnt), n.value,
+                                              ctypes.byref(n)), 'mh_sam2aln_ins_counts')
+        return ids, cut, pos, cnt
 
     @staticmethod
     def _bad_cycle_args(bad_cycles):

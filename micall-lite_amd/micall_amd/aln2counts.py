@@ -74,6 +74,8 @@ _SCHEMA = {
     'nuc': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT'),
     'nuc_detail': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
                   ['N', 'del', 'clip', 'coverage'],
+    'nuc_detail_ins': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
+                      ['N', 'del', 'clip', 'coverage', 'ins'],
     'conseq': ['region', 'q-cutoff', 'consensus-percent-cutoff', 'offset', 'sequence'],
     'nuc_variants': ['seed', 'qcut', 'region', 'index', 'count', 'seq'],
     'failed': ['seed', 'region', 'qcut', 'queryseq', 'refseq'],
@@ -505,8 +507,9 @@ class SequenceReport(object):
     def write_failure_header(self, fail_file):
         _csv_writer(fail_file, 'failed').writeheader()
 
-    def write_nuc_detail_header(self, nuc_detail_file):
-        _csv_writer(nuc_detail_file, 'nuc_detail').writeheader()
+    def write_nuc_detail_header(self, nuc_detail_file, insertions=False):
+        """insertions: the rows will end with the ins column."""
+        _csv_writer(nuc_detail_file, 'nuc_detail_ins' if insertions else 'nuc_detail').writeheader()
 
     # ---- bodies ----
     def write_amino_counts(self, amino_file, coverage_summary=None):
@@ -557,20 +560,27 @@ class SequenceReport(object):
         positions when the seed has no coordinate region."""
         csv.writer(nuc_file, lineterminator=os.linesep).writerows(self._nuc_lines(4)[0])
 
-    def write_nuc_detail(self, nuc_detail_file, clipping=None):
+    def write_nuc_detail(self, nuc_detail_file, clipping=None, insertions=None):
         """nuc.csv's rows (not in the reference) followed by what they leave
         out: the N and deletion counts of the position, the units that
         soft-clip it, and coverage = A + C + G + T + N + del, the depth
         write_consensus tests against min_coverage.  clipping: {seed:
         {consensus position: count}} of sam2aln's clipping.csv, None to leave
         the clip column empty.  query.nuc.pos ignores the reading frame, so
-        the consensus position of a row is query.nuc.pos - frame."""
+        the consensus position of a row is query.nuc.pos - frame.
+        insertions: {seed: {(q-cutoff, pos): count}} of sam2aln's
+        conseq_ins.csv summed over the strings, None for no ins column; with
+        it every row ends with ins, the units that carry an insertion after
+        the row's consensus position at the row's cutoff."""
         lines, frames = self._nuc_lines(6)
         clips = None if clipping is None else clipping.get(self.seed, {})
+        inserts = None if insertions is None else insertions.get(self.seed, {})
         for line, f in zip(lines, frames):
             query = line[3]
             clip = '' if clips is None else 0 if query == '' else clips.get(query - f, 0)
             line[11:] = [clip, sum(line[5:11])]
+            if inserts is not None:
+                line.append(0 if query == '' else inserts.get((int(self.qcut), query - f), 0))
         csv.writer(nuc_detail_file, lineterminator=os.linesep).writerows(lines)
 
     def write_consensus(self, conseq_file, min_coverage=100):
@@ -825,7 +835,7 @@ _SHARD = None      # the job's Shard while a sharded aln2counts runs (InsertionW
 def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
                coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
-               nuc_detail_csv=None):
+               nuc_detail_csv=None, conseq_ins_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -834,7 +844,9 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     reference's does.  nuc_detail_csv takes nuc.csv's rows with the N,
     deletion, soft-clip and coverage counts (SequenceReport.write_nuc_detail);
     clipping_csv is the input its clip column comes from, sam2aln's
-    clipping.csv (None: the column stays empty).
+    clipping.csv (None: the column stays empty).  conseq_ins_csv is an input
+    too, sam2aln's conseq_ins.csv: with it nuc_detail_csv's rows end with an
+    ins column, the units that carry an insertion after the position.
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -864,7 +876,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                 _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
-                            nuc_detail_csv=nuc_detail_csv)
+                            nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -872,7 +884,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
         try:
             _aln2counts(aligned_csv, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5],
                         callback if stage.active else None, outs[6], json, groups=groups,
-                        clipping_csv=clipping_csv, nuc_detail_csv=outs[8])
+                        clipping_csv=clipping_csv, nuc_detail_csv=outs[8],
+                        conseq_ins_csv=conseq_ins_csv)
         finally:
             _SHARD = None
 
@@ -934,7 +947,7 @@ def _load_sharded(sh, aligned_csv):
 
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
-                variants_csv=None, clipping_csv=None, nuc_detail_csv=None):
+                variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -956,8 +969,9 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
         per_run.append(lambda: report.write_variants(variants_csv))
     if nuc_detail_csv is not None:
         clipping = None if clipping_csv is None else _read_clipping(clipping_csv)
-        report.write_nuc_detail_header(nuc_detail_csv)
-        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping))
+        insertions = None if conseq_ins_csv is None else _read_conseq_ins(conseq_ins_csv)
+        report.write_nuc_detail_header(nuc_detail_csv, insertions is not None)
+        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -1000,6 +1014,17 @@ def _read_clipping(clipping_csv):
     return clipping
 
 
+def _read_conseq_ins(conseq_ins_csv):
+    """{refname: {(qcut, pos): count summed over the strings}} of sam2aln's
+    conseq_ins.csv."""
+    insertions = {}
+    for row in csv.DictReader(conseq_ins_csv):
+        per_ref = insertions.setdefault(row['refname'], {})
+        key = int(row['qcut']), int(row['pos'])
+        per_ref[key] = per_ref.get(key, 0) + int(row['count'])
+    return insertions
+
+
 def _arguments():
     cli = argparse.ArgumentParser(description='aln2counts on the MI355X: counts, consensus and '
                                               'insertions from aligned.csv.')
@@ -1016,6 +1041,8 @@ def _arguments():
                      help='output: top nucleotide variants of every coordinate region')
     cli.add_argument('--clipping_csv', type=argparse.FileType('r'),
                      help="input: sam2aln's clipping.csv, for the clip column of nuc_detail_csv")
+    cli.add_argument('--conseq_ins_csv', type=argparse.FileType('r'),
+                     help="input: sam2aln's conseq_ins.csv, for an ins column in nuc_detail_csv")
     cli.add_argument('--nuc_detail_csv', type=argparse.FileType('w'),
                      help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
     return cli.parse_args()
@@ -1028,7 +1055,8 @@ def main():
     a = _arguments()
     aln2counts(a.aligned_csv, a.nuc_csv, a.amino_csv, a.coord_ins_csv, a.conseq_csv,
                a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv,
-               clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv)
+               clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv,
+               conseq_ins_csv=a.conseq_ins_csv)
 
 
 if __name__ == '__main__':

@@ -36,6 +36,15 @@ number of merged units that soft-clip it while no mate aligns it
 (refname,pos,count), counted on the device from the rows the merge left
 there (mh_sam2aln_clipping: k_s2a_clip, k_s2a_clip_scan) on every route.
 A call without it launches and allocates nothing for it.
+
+conseq_ins_csv (optional, not in the reference): the insertions that the
+last remap pass left out of the consensus -- apply_cigar takes them out of
+the read and aligned.csv has no trace of them -- merged per unit and
+q-cutoff as the reference's merge_inserts merges them (sam2aln.py:240-273)
+and counted per distinct string: refname,qcut,pos,insert,count, pos the
+consensus position the insertion follows (not insert.csv's read-derived
+pos).  Counted on the device like the clipping (mh_sam2aln_conseq_ins:
+k_s2a_ins_rec, k_s2a_ins_merge, k_s2a_ins_tab), only when asked for.
 """
 import argparse
 import os
@@ -69,13 +78,14 @@ def _cutoff_list(q_cutoffs):
 
 
 def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None,
-            clipping_csv=None):
+            clipping_csv=None, conseq_ins_csv=None):
     """sam2aln.sam2aln (sam2aln.py:395-478).  q_cutoffs: the list of quality
     cutoffs, None for the module's SAM2ALN_Q_CUTOFFS (where the reference's
     users set it).  In a sharded job every rank does its share
     (_sam2aln_sharded); when remap.csv cannot be split that way, rank 0
     computes and writes while the other ranks wait (session.writer_stage).
-    clipping_csv: an open file for the soft-clip counts, None for none."""
+    clipping_csv: an open file for the soft-clip counts, None for none;
+    conseq_ins_csv: one for the merged insertions."""
     cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
@@ -83,9 +93,10 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     session.aligned_forget()     # recorded again below, once aligned.csv is these results
     use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
     if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts,
-                                           clipping_csv):
+                                           clipping_csv, conseq_ins_csv):
         return
-    with session.writer_stage(aligned_csv, insert_csv, failed_csv, clipping_csv) as stage:
+    with session.writer_stage(aligned_csv, insert_csv, failed_csv, clipping_csv,
+                              conseq_ins_csv) as stage:
         if not stage.active:
             return
         ctx = session.context()
@@ -104,7 +115,9 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
             text = session.read_text(remap_csv)
             ctx.sam2aln_csv(text, q_cutoffs=cuts, max_prop_n=MAX_PROP_N)
         if clipping_csv:
-            _write_clipping(ctx, clipping_csv)
+            _write_side(clipping_csv, ctx.sam2aln_clipping_write, ctx.sam2aln_clipping)
+        if conseq_ins_csv:
+            _write_side(conseq_ins_csv, ctx.sam2aln_conseq_ins_write, ctx.sam2aln_conseq_ins)
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
                 start = _write_output(ctx, which, handle)
@@ -115,7 +128,8 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
 SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitters
 
 
-def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None, clipping_csv=None):
+def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None, clipping_csv=None,
+                     conseq_ins_csv=None):
     """This rank's share of sam2aln.  False (on every rank, before any
     output is written) when the job must fall back to rank 0 alone: more
     than one q-cutoff (every rank holds the same list, so none has to ask),
@@ -147,6 +161,8 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
     names, first = ctx.sam2aln_part_names(part['names'])
     if clipping_csv:
         _clipping_sharded(sh, ctx, names, clipping_csv)
+    if conseq_ins_csv:
+        _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv)
     texts = sh.all_gather_bytes('\n'.join(names).encode())
     firsts = sh.all_gather_bytes(np.asarray(first, dtype=np.int64).tobytes())
     pairs = sh._gather_sizes([part['pair_units']])[:, 0]
@@ -193,7 +209,7 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
             o.finish()
     out.finish()
     sh.barrier()             # every rank's rows are in the files
-    for h in (aligned_csv, insert_csv, failed_csv, clipping_csv):
+    for h in (aligned_csv, insert_csv, failed_csv, clipping_csv, conseq_ins_csv):
         if h and sh.rank == 0:
             h.flush()
     return True
@@ -223,15 +239,37 @@ def _clipping_sharded(sh, ctx, names, clipping_csv):
     w.writerows((name, p, total[name, p]) for name, p in sorted(total))
 
 
-def _write_clipping(ctx, handle):
-    """clipping.csv, as _write_output writes the other three."""
+def _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv):
+    """conseq_ins.csv of a sharded call (one q-cutoff): every rank counts the
+    insertions of its own units on its device, the (name, pos, insert, count)
+    lists -- each rank's own conseq_ins.csv rows -- are all-gathered, and
+    rank 0 adds them up and writes in the file's order."""
+    import csv
+    import io
+    parts = sh.all_gather_bytes(ctx.sam2aln_conseq_ins().encode())
+    if sh.rank != 0:
+        return
+    total = {}
+    for part in parts:
+        for row in csv.DictReader(io.StringIO(part.decode())):
+            key = row['refname'], int(row['pos']), row['insert']
+            total[key] = total.get(key, 0) + int(row['count'])
+    w = csv.writer(conseq_ins_csv, lineterminator='\n')
+    w.writerow(['refname', 'qcut', 'pos', 'insert', 'count'])
+    w.writerows((name, cuts[0], pos, ins, n) for (name, pos, ins), n in
+                sorted(total.items(), key=lambda kv: (kv[0][0], kv[0][1], -kv[1], kv[0][2].encode())))
+
+
+def _write_side(handle, write, text):
+    """clipping.csv or conseq_ins.csv, as _write_output writes the other
+    three: write(fd, offset) for a plain file, else text() through the handle."""
     from .sharded_io import SharedOutput
     out = SharedOutput(None, handle)
     if out.direct:
-        out.end += ctx.sam2aln_clipping_write(out.fd, int(out.end))
+        out.end += write(out.fd, int(out.end))
         out.finish()
     else:
-        handle.write(ctx.sam2aln_clipping())
+        handle.write(text())
 
 
 def _write_output(ctx, which, handle):
@@ -283,6 +321,9 @@ def parseArgs():
     parser.add_argument('--clipping_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
                         help='<output> CSV of soft-clipped positions that no mate aligns, '
                              'counted per consensus position')
+    parser.add_argument('--conseq_ins_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
+                        help='<output> CSV of the insertions left out of the consensus, merged per '
+                             'pair and counted per consensus position and string')
     return parser.parse_args()
 
 
@@ -290,7 +331,7 @@ def main():
     args = parseArgs()
     sam2aln(remap_csv=args.remap_csv, aligned_csv=args.aligned_csv, insert_csv=args.insert_csv,
             failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut,
-            clipping_csv=args.clipping_csv)
+            clipping_csv=args.clipping_csv, conseq_ins_csv=args.conseq_ins_csv)
 
 
 if __name__ == '__main__':
