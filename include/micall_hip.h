@@ -41,7 +41,8 @@
  *      InsertionWriter.write (:748-811)
  *          -> mh_a2c_load_csv / mh_a2c_load_rows, mh_a2c_counts,
  *             mh_a2c_inserts; the nucleotide variants of the coordinate
- *             regions (:346-375, :537-549) -> mh_a2c_variants.
+ *             regions (:346-375, :537-549) -> mh_a2c_variants; the codons
+ *             count_aminos drops (:595-603) -> mh_a2c_codon_detail.
  *
  * Conventions: every function returns 0 on success, -1 on traceback failure
  * (mh_gotoh_align only), -2 on out-of-memory, -3 on a bad argument, -4 on a
@@ -722,6 +723,18 @@ int mh_a2c_group(mh_ctx *ctx, int slot, int64_t g, int64_t *info5, char *names, 
  * touched (the Counter has no such key). */
 int mh_a2c_counts(mh_ctx *ctx, int slot, int64_t g, int frame, uint32_t *aa_count,
                   uint32_t *aa_first, uint32_t *nuc_count, uint32_t *nuc_first);
+/* The codons of group g, frame 0..2 that mh_a2c_counts' 21 letters leave out
+ * because they translate to no amino acid: xpd [codon][3] = X (three of
+ * A C G T N, ambiguous), partial ('-' or 'n' beside a base) and del (three
+ * '-' of the read itself, not the padding around it), each the summed count
+ * column of its rows; codons 0 .. info5[2 + frame] - 1.  A codon without any
+ * base that is no deletion (padding, the gap between the mates) is counted
+ * nowhere.  The first call after a load counts all groups and frames of the
+ * slot in one launch (k_a2c_detail, over the rows and chunks the load left
+ * on the device); later calls copy.  After mh_a2c_part_count the counters
+ * are those of this rank's rows (the caller adds the ranks up).  -3 for a
+ * slot without a load, a bad group or frame. */
+int mh_a2c_codon_detail(mh_ctx *ctx, int slot, int64_t g, int frame, uint32_t *xpd);
 /* InsertionWriter.write's read loop (:779-795) over the rows of group g for
  * the codon ranges [left[k], right[k]) in reading frame `frame`: distinct
  * amino-acid strings per range with their summed counts, in (range, first

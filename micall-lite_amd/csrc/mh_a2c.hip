@@ -18,6 +18,10 @@
 //                 Counter insertion order that most_common() breaks ties by
 //                 (:624, :668).  One global atomic per touched counter
 //                 flushes the chunk.
+//   k_a2c_detail  the codons k_a2c_count drops because they translate to no
+//                 amino acid, sorted into X / partial / del over the same
+//                 chunks and lanes; run only when mh_a2c_codon_detail asks
+//                 (amino_detail.csv; the rule: tests/amino_detail_oracle.py).
 //   k_a2c_stage, k_a2c_bin_count / _scan / _fill
 //                 the rows and the bin lists built on the device from the
 //                 results sam2aln left there (mh_a2c_load_resident): what the
@@ -123,6 +127,12 @@ struct A2CState {
     int32_t *d_bin_rows = nullptr;
     A2CChunk *d_chunks = nullptr;
     uint32_t *d_cnt = nullptr, *d_first = nullptr;
+    // mh_a2c_codon_detail: the chunks of the last load that counted, and the
+    // X / partial / del counters k_a2c_detail makes of them on the first request
+    size_t n_chunks = 0;
+    bool counted = false, det_ready = false;
+    uint32_t *d_det = nullptr;
+    std::vector<uint32_t> h_det;              // [bin][frame * 21 + codon][3]
     // mh_a2c_load_resident: the rows were built on the device (rows is
     // empty; every group's first row has local 0) from these uploads
     bool dev_rows = false;
@@ -214,6 +224,72 @@ __global__ __launch_bounds__(256) void k_a2c_count(A2CCountArgs A)
         if (s_cnt[i]) atomicAdd(&A.cnt[base + i], s_cnt[i]);
         atomicMin(&A.first[base + i], fr);
     }
+}
+
+// ---- the codons k_a2c_count leaves out (amino_detail.csv) -----------------
+// A codon whose translation is not one of the 21 letters is counted nowhere
+// by k_a2c_count.  k_a2c_detail walks the same chunks with the same lanes and
+// sorts those codons: all three characters '-' of the read itself (not the
+// padding around it) is a deletion; no base at all (padding, the gap between
+// the mates) is nothing; a '-' or 'n' beside a base is a partial codon; three
+// of A C G T N are an ambiguous one.  Per lane three LDS counters (stride 3:
+// odd, distinct banks), no first row; one global atomic per non-zero counter
+// flushes the chunk.
+constexpr int A2C_DET = 3;                              // X, partial, del
+constexpr int A2C_DET_CELLS = A2C_LANES * A2C_DET;      // counters per bin (3 frames)
+enum { A2C_DET_X = 0, A2C_DET_PARTIAL = 1, A2C_DET_DEL = 2 };
+
+struct A2CDetailArgs {
+    const uint8_t *text;
+    const A2CRow *rows;
+    const int32_t *bin_rows;
+    const A2CChunk *chunks;
+    const int8_t *code;
+    const uint8_t *cls;
+    uint32_t *det;        // [bin][frame * 21 + codon][3]
+};
+
+__global__ __launch_bounds__(256) void k_a2c_detail(A2CDetailArgs A)
+{
+    __shared__ uint32_t s_det[A2C_DET_CELLS];
+    __shared__ int8_t s_code[512];
+    __shared__ uint8_t s_cls[256];
+    const A2CChunk ch = A.chunks[blockIdx.x];
+    if (threadIdx.x < A2C_DET_CELLS) s_det[threadIdx.x] = 0;
+    s_code[threadIdx.x] = A.code[threadIdx.x];
+    s_code[threadIdx.x + 256] = A.code[threadIdx.x + 256];
+    s_cls[threadIdx.x] = A.cls[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int f = lane / A2C_W;
+    const int j = ch.codon0 + lane - A2C_W * f;
+    uint32_t *cc = s_det + lane * A2C_DET;
+    for (int64_t i = ch.beg + (threadIdx.x >> 6); i < ch.end; i += 4) {
+        if (lane >= A2C_LANES) continue;
+        const A2CRow R = A.rows[A.bin_rows[i]];
+        if (j < R.off / 3 || j >= (f + R.off + R.len + 2) / 3) continue;
+        const int q0 = 3 * j - f - R.off;
+        const uint8_t *s = A.text + R.soff;
+        int c[3], inside = 0;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int q = q0 + t;
+            const bool in = q >= 0 && q < R.len;
+            c[t] = in ? s_cls[s[q]] : A2C_DASH;
+            inside += in;
+        }
+        if (s_code[64 * c[0] + 8 * c[1] + c[2]] < A2C_NAA) continue;     // amino.csv's own
+        const int dashes = (c[0] == A2C_DASH) + (c[1] == A2C_DASH) + (c[2] == A2C_DASH);
+        const int bases = (c[0] < A2C_DASH) + (c[1] < A2C_DASH) + (c[2] < A2C_DASH);
+        int k;
+        if (dashes == 3 && inside == 3) k = A2C_DET_DEL;
+        else if (bases == 0) continue;
+        else k = bases == 3 ? A2C_DET_X : A2C_DET_PARTIAL;
+        atomicAdd(&cc[k], R.cnt);
+    }
+    __syncthreads();
+    if (threadIdx.x < A2C_DET_CELLS && s_det[threadIdx.x])
+        atomicAdd(&A.det[(size_t)ch.bin * A2C_DET_CELLS + threadIdx.x], s_det[threadIdx.x]);
 }
 
 // The bins of its group a row reaches: every codon of every frame it touches
@@ -639,7 +715,9 @@ static void a2c_free_device(A2CState &S)
     hipFree(S.d_text); hipFree(S.d_cls); hipFree(S.d_code); hipFree(S.d_rows);
     hipFree(S.d_bin_rows); hipFree(S.d_chunks); hipFree(S.d_cnt); hipFree(S.d_first);
     hipFree(S.d_order); hipFree(S.d_gfirst); hipFree(S.d_gbin0); hipFree(S.d_ncod);
-    hipFree(S.d_bstart); hipFree(S.d_bcur);
+    hipFree(S.d_bstart); hipFree(S.d_bcur); hipFree(S.d_det);
+    S.d_det = nullptr;
+    S.counted = S.det_ready = false;
     S.d_order = S.d_gfirst = S.d_gbin0 = S.d_ncod = nullptr;
     S.d_bstart = S.d_bcur = nullptr;
     S.d_text = S.d_cls = nullptr;
@@ -897,6 +975,8 @@ static int a2c_count_chunks(Ctx &c, A2CState &S, size_t n_chunks)
 {
     hipStream_t s = c.stream;
     const size_t cells = (size_t)S.n_bins * A2C_CELLS;
+    S.counted = S.det_ready = false;
+    S.n_chunks = n_chunks;
     if (int st = a2c_reserve(S, S.d_cnt, sizeof(uint32_t) * cells)) return st;
     if (int st = a2c_reserve(S, S.d_first, sizeof(uint32_t) * cells)) return st;
     if (cells) {
@@ -921,6 +1001,31 @@ static int a2c_count_chunks(Ctx &c, A2CState &S, size_t n_chunks)
     }
     MH_HIP(hipStreamSynchronize(s));
     prof_flush(c);
+    S.counted = true;
+    return 0;
+}
+
+// k_a2c_detail over the chunks the last load left on the device, one launch
+// for all groups of the slot; the counters fetched
+static int a2c_detail_run(Ctx &c, A2CState &S)
+{
+    hipStream_t s = c.stream;
+    const size_t cells = (size_t)S.n_bins * A2C_DET_CELLS;
+    if (int st = a2c_reserve(S, S.d_det, sizeof(uint32_t) * cells)) return st;
+    if (cells) MH_HIP(hipMemsetAsync(S.d_det, 0, sizeof(uint32_t) * cells, s));
+    if (S.n_chunks) {
+        A2CDetailArgs a{S.d_text, S.d_rows, S.d_bin_rows, S.d_chunks, S.d_code, S.d_cls, S.d_det};
+        const int p0 = prof_begin(c, "k_a2c_detail");
+        hipLaunchKernelGGL(k_a2c_detail, dim3((unsigned)S.n_chunks), dim3(256), 0, s, a);
+        prof_end(c, p0);
+        MH_HIP(hipGetLastError());
+    }
+    S.h_det.resize(cells);
+    if (cells)
+        MH_HIP(hipMemcpyAsync(S.h_det.data(), S.d_det, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    prof_flush(c);
+    S.det_ready = true;
     return 0;
 }
 
@@ -1109,6 +1214,7 @@ extern "C" int mh_a2c_load_csv(mh_ctx *ctx, int slot, const char *text, int64_t 
     MH_HIP(hipSetDevice(c.device));
     A2CState &S = *a2c_state(c, slot);
     a2c_clear_inserts(S);
+    S.counted = S.det_ready = false;
     if (S.part_text) {       // a part left open by a sharded load that fell back
         unmap_text_file(S.part_text, S.part_len);
         S.part_text = nullptr;
@@ -1309,6 +1415,7 @@ extern "C" int mh_a2c_load_resident(mh_ctx *ctx, int slot, const char *codon_cha
     MH_HIP(hipSetDevice(c.device));
     A2CState &S = *a2c_state(c, slot);
     a2c_clear_inserts(S);
+    S.counted = S.det_ready = false;
     if (S.part_text) {       // a part left open by a sharded load that fell back
         unmap_text_file(S.part_text, S.part_len);
         S.part_text = nullptr;
@@ -1345,6 +1452,7 @@ extern "C" int mh_a2c_load_rows(mh_ctx *ctx, int slot, int64_t n_rows, const cha
     MH_HIP(hipSetDevice(c.device));
     A2CState &S = *a2c_state(c, slot);
     a2c_clear_inserts(S);
+    S.counted = S.det_ready = false;
     auto t0 = std::chrono::steady_clock::now();
     if (int st = a2c_tables(S, codon_chars)) return st;
     if (group_first[0] != 0 || group_first[n_groups] != n_rows) {
@@ -1437,6 +1545,35 @@ extern "C" int mh_a2c_counts(mh_ctx *ctx, int slot, int64_t g, int frame, uint32
         memcpy(aa_first + (size_t)j * A2C_NAA, &S.h_first[at], 4 * A2C_NAA);
         memcpy(nuc_count + (size_t)j * 18, &S.h_cnt[at + A2C_NAA], 4 * 18);
         memcpy(nuc_first + (size_t)j * 18, &S.h_first[at + A2C_NAA], 4 * 18);
+    }
+    return 0;
+}
+
+extern "C" int mh_a2c_codon_detail(mh_ctx *ctx, int slot, int64_t g, int frame, uint32_t *xpd)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || frame < 0 || frame > 2) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    if (!S.counted) { set_error("mh_a2c_codon_detail: nothing is loaded in slot %d", slot); return -3; }
+    const int64_t ng = (int64_t)S.g_first.size() - 1;
+    if (g < 0 || g >= ng) { set_error("mh_a2c_codon_detail: no group %lld", (long long)g); return -3; }
+    const int n = S.g_ncod[3 * g + frame];
+    if (n && !xpd) return -3;
+    if (!S.det_ready) {
+        MH_HIP(hipSetDevice(c.device));
+        int st = 0;
+        try {
+            st = a2c_detail_run(c, S);
+        } catch (const std::exception &e) {
+            set_error("mh_a2c_codon_detail: out of memory (%s)", e.what());
+            st = -2;
+        }
+        if (st) return st;
+    }
+    for (int j = 0; j < n; ++j) {
+        const size_t at = (size_t)(S.g_bin0[g] + j / A2C_W) * A2C_DET_CELLS +
+                          (size_t)(A2C_W * frame + j % A2C_W) * A2C_DET;
+        memcpy(xpd + (size_t)j * A2C_DET, &S.h_det[at], 4 * A2C_DET);
     }
     return 0;
 }
@@ -1660,6 +1797,7 @@ extern "C" int mh_a2c_part_open(mh_ctx *ctx, int slot, int fd, int part, int par
     MH_HIP(hipSetDevice(c.device));
     A2CState &S = *a2c_state(c, slot);
     a2c_clear_inserts(S);
+    S.counted = S.det_ready = false;
     if (S.part_text) { unmap_text_file(S.part_text, S.part_len); S.part_text = nullptr; }
     S.part_open = false;
     if (int st = a2c_tables(S, codon_chars)) return st;

@@ -208,7 +208,8 @@ def _declare(L):
                           ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_a2c_counts': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P],
                           ctypes.c_int),
-        'mh_a2c_inserts': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P,
+        'mh_a2c_codon_detail': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _P], ctypes.c_int),
+        'mh_a2c_inserts':([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P,
                             _I64P], ctypes.c_int),
         'mh_a2c_insert_entries': ([_P, ctypes.c_int, _P, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
@@ -991,6 +992,14 @@ class Context:
         check(lib().mh_a2c_counts(self.h, slot, g, frame, _ptr(aa_c), _ptr(aa_f), _ptr(nt_c),
                                   _ptr(nt_f)), 'mh_a2c_counts')
         return aa_c[:ncod], aa_f[:ncod], nt_c[:ncod], nt_f[:ncod]
+
+    def a2c_codon_detail(self, slot, g, frame, ncod):
+        """[ncod, 3] uint32 of one group and frame: the X, partial and del
+        codons the 21 letters of a2c_counts leave out (mh_a2c_codon_detail;
+        the first call after a load launches k_a2c_detail)."""
+        xpd = np.zeros((max(ncod, 1), 3), np.uint32)
+        check(lib().mh_a2c_codon_detail(self.h, slot, g, frame, _ptr(xpd)), 'mh_a2c_codon_detail')
+        return xpd[:ncod]
 
     def a2c_inserts(self, slot, g, frame, lefts, rights):
         """[(range index, count, first row, amino-acid string)] in

@@ -34,6 +34,10 @@ unchanged.  Differences that never reach an output file:
     --variants_csv): the report write_nuc_variants was meant to write, counted
     on the device (mh_a2c_variants).  write_nuc_variants / nuc_variants_csv
     fail as the reference's do;
+  * the codons count_aminos drops because they translate to no amino acid
+    (aln2counts.py:595-603) are counted, as X, partial and del, only when
+    asked for (SequenceReport.write_amino_detail, aln2counts(amino_detail_csv=),
+    --amino_detail_csv): k_a2c_detail through mh_a2c_codon_detail;
   * an InsertionWriter fed by a SequenceReport reads the run's rows from the
     device, so its nuc_seqs stays empty;
   * characters other than A C G T N - n, negative offsets and counts of 2**32
@@ -76,6 +80,8 @@ _SCHEMA = {
                   ['N', 'del', 'clip', 'coverage'],
     'nuc_detail_ins': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
                       ['N', 'del', 'clip', 'coverage', 'ins'],
+    'amino_detail': ['seed', 'region', 'q-cutoff', 'query.aa.pos', 'refseq.aa.pos'] + list(AMINO_ALPHABET) +
+                    ['X', 'partial', 'del', 'ins', 'clip', 'coverage'],
     'conseq': ['region', 'q-cutoff', 'consensus-percent-cutoff', 'offset', 'sequence'],
     'nuc_variants': ['seed', 'qcut', 'region', 'index', 'count', 'seq'],
     'failed': ['seed', 'region', 'qcut', 'queryseq', 'refseq'],
@@ -237,6 +243,7 @@ class _Frame(object):
         self.nt_first = nt_first.reshape(-1, 3, 6)
         self.has = (aa_first != _NONE).any(axis=1)      # the codon's Counter is not empty
         self._consensus = None
+        self.xpd = None       # X / partial / del per codon, once asked for (_codon_detail)
 
     def consensus(self):
         """Amino-acid consensus of the frame: the most counted amino acid of
@@ -389,6 +396,7 @@ class SequenceReport(object):
         self._run = run
         self._variants_counted = False
         self.variant_stats = None
+        self._job_detail = None
         if run is not None:
             self.seed, self.qcut = run.seed, run.qcut
             self.insert_writer.start_group(run.seed, run.qcut)
@@ -491,6 +499,21 @@ class SequenceReport(object):
             out[hit] = table(self._frames[cmap.frame])[cmap.conseq_index[hit]]
         return out
 
+    def _codon_detail(self, f):
+        """(codons of frame f, 3) X, partial and del counts: the codons read
+        there that translate to none of the 21 letters (mh_a2c_codon_detail;
+        the first request after a load runs k_a2c_detail over every group of
+        the slot, nothing is fetched before).  In a sharded job the tables
+        are the job's, added up over the ranks (_job_detail)."""
+        frame = self._frames[f]
+        if frame.xpd is None:
+            run = self._run
+            if self._job_detail is not None:
+                frame.xpd = self._job_detail[f]
+            else:
+                frame.xpd = run.ctx.a2c_codon_detail(run.slot, run.group, f, frame.ncod).astype(np.int64)
+        return frame.xpd
+
     # ---- headers ----
     def write_amino_header(self, amino_file):
         _csv_writer(amino_file, 'amino').writeheader()
@@ -507,28 +530,68 @@ class SequenceReport(object):
     def write_failure_header(self, fail_file):
         _csv_writer(fail_file, 'failed').writeheader()
 
+    def write_amino_detail_header(self, amino_detail_file):
+        _csv_writer(amino_detail_file, 'amino_detail').writeheader()
+
     def write_nuc_detail_header(self, nuc_detail_file, insertions=False):
         """insertions: the rows will end with the ins column."""
         _csv_writer(nuc_detail_file, 'nuc_detail_ins' if insertions else 'nuc_detail').writeheader()
 
     # ---- bodies ----
-    def write_amino_counts(self, amino_file, coverage_summary=None):
-        """Amino-acid counts per coordinate position, regions in name order;
-        the region with the highest mean count goes to coverage_summary."""
-        out = csv.writer(amino_file, lineterminator=os.linesep)
+    def _amino_lines(self):
+        """amino.csv's rows region by region, regions in name order: (name,
+        the region's map, its (positions, 21) counts, its rows)."""
         for name in sorted(self.reports):
             cmap = self._coord_maps[name]
             if not len(cmap):
                 continue
             counts = self._gather(cmap, lambda fr: fr.aa_cnt, (len(AMINO_ALPHABET),))
             query = ['' if k < 0 else str(k + 1) for k in cmap.conseq_index.tolist()]
-            out.writerows([self.seed, name, self.qcut, q, p] + c for q, p, c in
-                          zip(query, cmap.positions.tolist(), counts.tolist()))
+            yield name, cmap, counts, [[self.seed, name, self.qcut, q, p] + c for q, p, c in
+                                       zip(query, cmap.positions.tolist(), counts.tolist())]
+
+    def write_amino_counts(self, amino_file, coverage_summary=None):
+        """Amino-acid counts per coordinate position, regions in name order;
+        the region with the highest mean count goes to coverage_summary."""
+        out = csv.writer(amino_file, lineterminator=os.linesep)
+        for name, cmap, counts, lines in self._amino_lines():
+            out.writerows(lines)
             if coverage_summary is not None:
                 mean = float(counts.sum()) / len(cmap)
                 if mean > coverage_summary.get('avg_coverage', -1):
                     coverage_summary.update(avg_coverage=mean, coverage_region=name,
                                             region_width=len(cmap))
+
+    def write_amino_detail(self, amino_detail_file, clipping=None, insertions=None):
+        """amino.csv's rows (not in the reference) followed by what they leave
+        out.  X, partial and del are the reads of the position's consensus
+        codon, in the region's frame, that count_aminos drops because they
+        translate to no amino acid: three of A C G T N with an ambiguous
+        translation; a '-' or the gap between the mates beside a base (a
+        deletion that is no multiple of three, a read end); all three bases
+        deleted within the read.  coverage = the 21 letters + X + partial +
+        del.  With k = query.aa.pos - 1 and f the region's frame the codon is
+        consensus positions 3k - f + 1 .. 3k - f + 3 (write_nuc_detail's
+        arithmetic): ins is the sum over them of the units that carry an
+        insertion there at the row's cutoff, clip the largest of their
+        soft-clip counts -- a lower bound of the units that clip any base of
+        the codon, since a unit clipping two of them is one unit in each
+        count.  clipping: {seed: {consensus position: count}} of sam2aln's
+        clipping.csv; insertions: {seed: {(q-cutoff, pos): count}} of its
+        conseq_ins.csv summed over the strings; None leaves the column
+        empty.  Both are 0 without an entry or a query position."""
+        clips = None if clipping is None else clipping.get(self.seed, {})
+        inserts = None if insertions is None else insertions.get(self.seed, {})
+        out = csv.writer(amino_detail_file, lineterminator=os.linesep)
+        for name, cmap, counts, lines in self._amino_lines():
+            f = cmap.frame
+            xpd = self._gather(cmap, lambda fr: self._codon_detail(f), (3,))
+            for line, k, three in zip(lines, cmap.conseq_index.tolist(), xpd.tolist()):
+                codon = () if k < 0 else range(3 * k - f + 1, 3 * k - f + 4)
+                ins = '' if inserts is None else sum(inserts.get((int(self.qcut), p), 0) for p in codon)
+                clip = '' if clips is None else max([clips.get(p, 0) for p in codon], default=0)
+                line += three + [ins, clip, sum(line[5:]) + sum(three)]
+            out.writerows(lines)
 
     def _nuc_lines(self, classes):
         """nuc.csv's rows with the first `classes` of the A C G T N - counts
@@ -835,7 +898,7 @@ _SHARD = None      # the job's Shard while a sharded aln2counts runs (InsertionW
 def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
                coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
-               nuc_detail_csv=None, conseq_ins_csv=None):
+               nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -847,6 +910,11 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     clipping.csv (None: the column stays empty).  conseq_ins_csv is an input
     too, sam2aln's conseq_ins.csv: with it nuc_detail_csv's rows end with an
     ins column, the units that carry an insertion after the position.
+    amino_detail_csv takes amino.csv's rows with the X, partial, del, ins, clip
+    and coverage columns (SequenceReport.write_amino_detail): the codons read
+    at the position that amino.csv leaves out, counted on the device only
+    when this is asked for; its ins and clip columns come from the same two
+    inputs (read once for both detail files) and stay empty without them.
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -856,13 +924,15 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     When aligned.csv cannot be split (not a plain file on every rank, '\r'
     or quoted fields), rank 0 computes alone while the others wait; so it
     does when any rank was given variants_csv (the variants are counted over
-    all rows of a run at once, not merged across ranks)."""
+    all rows of a run at once, not merged across ranks).  When any rank was
+    given amino_detail_csv every rank counts the codon classes of its own rows
+    and the tables are added up."""
     global _SHARD
     sh = session.shard()
     SHARD_STATS.clear()
     session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
-               coverage_summary_csv, variants_csv, nuc_detail_csv)
+               coverage_summary_csv, variants_csv, nuc_detail_csv, amino_detail_csv)
     with session.writer_stage(*handles) as stage:
         split = sh is not None
         if split:
@@ -870,13 +940,16 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
             if not _agree_ok(sh, variants_csv is None):    # asked for on some rank
                 split = False
                 SHARD_STATS.update(mode='unsplit', reason='variants_csv')
+        # asked for on some rank: then every rank enters the sum of the tables
+        job_detail = split and not _agree_ok(sh, amino_detail_csv is None)
         groups = _load_sharded(sh, aligned_csv) if split else None
         if groups is None:
             if stage.active:
                 _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
-                            nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv)
+                            nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv,
+                            amino_detail_csv=amino_detail_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -885,7 +958,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
             _aln2counts(aligned_csv, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5],
                         callback if stage.active else None, outs[6], json, groups=groups,
                         clipping_csv=clipping_csv, nuc_detail_csv=outs[8],
-                        conseq_ins_csv=conseq_ins_csv)
+                        conseq_ins_csv=conseq_ins_csv, amino_detail_csv=outs[9], job_detail=job_detail)
         finally:
             _SHARD = None
 
@@ -947,7 +1020,8 @@ def _load_sharded(sh, aligned_csv):
 
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
-                variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None):
+                variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None,
+                amino_detail_csv=None, job_detail=False):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -967,11 +1041,15 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if variants_csv is not None:
         report.write_nuc_variants_header(variants_csv)
         per_run.append(lambda: report.write_variants(variants_csv))
-    if nuc_detail_csv is not None:
+    if nuc_detail_csv is not None or amino_detail_csv is not None:
         clipping = None if clipping_csv is None else _read_clipping(clipping_csv)
         insertions = None if conseq_ins_csv is None else _read_conseq_ins(conseq_ins_csv)
+    if nuc_detail_csv is not None:
         report.write_nuc_detail_header(nuc_detail_csv, insertions is not None)
         per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions))
+    if amino_detail_csv is not None:
+        report.write_amino_detail_header(amino_detail_csv)
+        per_run.append(lambda: report.write_amino_detail(amino_detail_csv, clipping, insertions))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -998,12 +1076,34 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
                 aligned_csv.seek(0, 2)
         if groups is None:
             groups = ctx.a2c_load_csv(SLOT_REPORT, session.read_text(aligned_csv), _CODON_CHARS)
+    tables = _job_detail(ctx, groups) if job_detail else None
     for g in range(groups):
         report._read_group(ctx, SLOT_REPORT, g)
+        if tables is not None:
+            report._job_detail = tables[g]
         for step in per_run:
             step()
     if summary:
         summary_writer.writerow(summary)
+
+
+def _job_detail(ctx, groups):
+    """Per group the three frames' (codons, 3) X / partial / del tables of a
+    sharded job: every rank's counts of its own rows (mh_a2c_codon_detail
+    after mh_a2c_part_count), added up over the ranks in one collective that
+    every rank enters."""
+    from .sharded_io import _checked
+    ncod = [ctx.a2c_group(SLOT_REPORT, g)['ncod'] for g in range(groups)]
+    mine = _checked(_SHARD, lambda: [ctx.a2c_codon_detail(SLOT_REPORT, g, f, ncod[g][f]).astype(np.int64)
+                                     for g in range(groups) for f in range(3)])
+    total = _SHARD.sum_i64(np.concatenate([t.reshape(-1) for t in mine] + [np.zeros(1, np.int64)]))
+    tables, at = [], 0
+    for g in range(groups):
+        tables.append([])
+        for f in range(3):
+            tables[g].append(total[at:at + 3 * ncod[g][f]].reshape(-1, 3))
+            at += 3 * ncod[g][f]
+    return tables
 
 
 def _read_clipping(clipping_csv):
@@ -1040,11 +1140,13 @@ def _arguments():
     cli.add_argument('--variants_csv', type=argparse.FileType('w'),
                      help='output: top nucleotide variants of every coordinate region')
     cli.add_argument('--clipping_csv', type=argparse.FileType('r'),
-                     help="input: sam2aln's clipping.csv, for the clip column of nuc_detail_csv")
+                     help="input: sam2aln's clipping.csv, for the clip column of the detail files")
     cli.add_argument('--conseq_ins_csv', type=argparse.FileType('r'),
-                     help="input: sam2aln's conseq_ins.csv, for an ins column in nuc_detail_csv")
+                     help="input: sam2aln's conseq_ins.csv, for the ins column of the detail files")
     cli.add_argument('--nuc_detail_csv', type=argparse.FileType('w'),
                      help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
+    cli.add_argument('--amino_detail_csv', type=argparse.FileType('w'),
+                     help='output: amino.csv with X, partial, del, ins, clip and coverage counts')
     return cli.parse_args()
 
 
@@ -1056,7 +1158,7 @@ def main():
     aln2counts(a.aligned_csv, a.nuc_csv, a.amino_csv, a.coord_ins_csv, a.conseq_csv,
                a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv,
                clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv,
-               conseq_ins_csv=a.conseq_ins_csv)
+               conseq_ins_csv=a.conseq_ins_csv, amino_detail_csv=a.amino_detail_csv)
 
 
 if __name__ == '__main__':
