@@ -649,7 +649,7 @@ int mh_censor_staged_write(mh_ctx *ctx, mh_fastq *fq, int n_bad, const char *con
                            const int32_t *cycles, int dst_gzip, int fd, int64_t offset,
                            int64_t *written, int64_t *base_count, int64_t *score_sum);
 /* Host wall ms of the last call: [0] gunzip + record split, [1] upload +
- * k_censor (+ k_trim) + download, [2] rewrite + gzip. */
+ * k_censor (+ k_trim, k_primer) + download, [2] rewrite + gzip. */
 int mh_censor_timing(mh_ctx *ctx, double *ms3);
 /* 3' adapter trimming inside the censor pass (micall_amd.trim_fastqs; the
  * step bin/micall:133 names and does not have).  The adapters hold for this
@@ -675,6 +675,31 @@ int mh_censor_set_adapters(mh_ctx *ctx, int n1, const char *const *seqs1, int n2
  * k of direction d (0: read 1, 1: the others), bases[...] the bases they
  * lost.  16 entries each; zero after mh_censor_set_adapters. */
 int mh_censor_trim_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases);
+/* Anchored 5' primer trimming inside the censor pass (micall_amd.trim_fastqs):
+ * an amplicon read begins with the PCR primer that made it.  The primers hold
+ * for this context's following mh_censor_fastq / mh_censor_staged /
+ * mh_censor_staged_write calls; n1 = n2 = 0 clears them.  seqs1 (n1 of them)
+ * apply to the records whose header says read 1, seqs2 to all others: 0 to
+ * 256 primers each, 8 to 64 bases of ACGT.  max_errors[i], i = 0..64, is the
+ * number of errors allowed in a primer of i bases (0 <= max_errors[i] <
+ * max(i, 1) and i + max_errors[i] <= 127).  Anything else: -3 and a message
+ * that names the primer or the table entry.
+ * After k_censor (and k_trim, if adapters are set), k_primer compares each
+ * record's kept sequence line (n bases; an 'N' matches nothing) with each
+ * primer p (m bases) of its direction: D(j) = the unit-cost edit distance
+ * between all of p and r[0:j], j = 0..min(n, m + max_errors[m]).  (k, j) is
+ * a candidate when D(j) <= max_errors[m]; the larger m - D wins (then the
+ * smaller D, the larger j, the lower primer index k) and the record's
+ * sequence line is written from j to its kept length, its quality line from
+ * min(j, kept quality length).  A record cut to nothing stays as an empty
+ * record.  base_count / score_sum keep their meaning; the read-length cap
+ * of the adapters does not apply (only the first 127 bases are read). */
+int mh_censor_set_primers(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                          const char *const *seqs2, const int32_t *max_errors);
+/* What the last censor call trimmed: reads[d * 256 + k] records won by primer
+ * k of direction d (0: read 1, 1: the others), bases[...] the bases they
+ * lost at the front.  512 entries each; zero after mh_censor_set_primers. */
+int mh_censor_primer_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases);
 
 /* ---- aln2counts: replaces the per-read loops of aln2counts.py ---------- */
 /* aligned.csv text (refname, qcut, count, offset, seq columns) read as

@@ -19,9 +19,16 @@
 //             its read direction by a semi-global unit-cost edit distance
 //             (lane l = adapter row l + 1, skewed along the read); the
 //             kept lengths are lowered to the leftmost match's start
+//   k_primer  only with primers set (mh_censor_set_primers): one wave64 per
+//             read, lane l takes the primers l, l + 64, ... of its read
+//             direction, each anchored at the read's first base by Myers'
+//             bit-vector edit distance (the primer's rows in one 64-bit
+//             word, one column per read base); the winner's end is the
+//             record's lead, the bases the writer drops at the front
 //   host      records rewritten (header and '+' lines verbatim) and, for
 //             gzip output, compressed, in blocks of ~8 MB of records on
-//             every host thread (one gzip member per block: the member
+//             every host thread, sequence and quality lines from their lead
+//             to their kept length (one gzip member per block: the member
 //             boundaries depend on the input only, not on the thread count);
 //             the output is written with pwrite (mh_censor_write) or copied
 //             out (mh_censor_output)
@@ -62,6 +69,22 @@ struct TrimTab {
     uint8_t seq[2 * TRIM_MAXADAPT][TRIM_MAXLEN];
 };
 
+constexpr int PRIMER_MAX = 256;     // primers per read direction
+constexpr int PRIMER_MINLEN = 8;    // primer bases: the rows of one 64-bit word
+constexpr int PRIMER_MAXLEN = 64;
+constexpr int PRIMER_MAXCOL = 127;  // read columns looked at: 7 bits of the key, two loads a lane
+
+// the primers as k_primer reads them, slot = direction * PRIMER_MAX + index:
+// eq[d][c][k] has bit i set where primer k of direction d holds base "ACGT"[c]
+// at i; cols[d] is the largest len + err of the direction's list
+struct PrimerTab {
+    int32_t n[2];
+    int32_t cols[2];
+    int32_t len[2 * PRIMER_MAX];
+    int32_t err[2 * PRIMER_MAX];   // errors allowed in the whole primer
+    uint64_t eq[2][4][PRIMER_MAX];
+};
+
 struct CensorState {
     TextBuf text;                           // the FASTQ (censored in place)
     // per record: line starts (header, seq, '+', qual); the header line is
@@ -70,6 +93,7 @@ struct CensorState {
     std::vector<int32_t> sl, ql;            // seq / qual lengths, trailing whitespace stripped
     std::vector<int32_t> tile, sign;        // tile id (-1: no bad cycle) / +1, -1
     std::vector<int32_t> keep;              // 2 per record: kept seq / qual length
+    std::vector<int32_t> lead;              // per record, only with primers set: bases dropped in front
     int64_t base_count = 0, score_sum = 0;
     TextBuf out;                            // the censored file (gzip members or text)
     // set: the blocks are written to sink_fd from sink_pos as they are made
@@ -92,6 +116,14 @@ struct CensorState {
     int64_t trim_reads[2 * TRIM_MAXADAPT] = {}, trim_bases[2 * TRIM_MAXADAPT] = {};
     TrimTab *d_trim = nullptr;
     unsigned long long *d_tstat = nullptr;   // reads[16], bases[16]
+    // 5' primers of the following calls (mh_censor_set_primers) and what the
+    // last call trimmed, per direction * PRIMER_MAX + primer
+    bool primer_on = false;
+    PrimerTab primer{};
+    int64_t primer_reads[2 * PRIMER_MAX] = {}, primer_bases[2 * PRIMER_MAX] = {};
+    PrimerTab *d_primer = nullptr;
+    int32_t *d_lead = nullptr;
+    unsigned long long *d_pstat = nullptr;   // reads[512], bases[512]
 };
 
 static void censor_free_device(CensorState &C)
@@ -100,6 +132,8 @@ static void censor_free_device(CensorState &C)
     hipFree(C.d_tile); hipFree(C.d_sign); hipFree(C.d_keep); hipFree(C.d_bad); hipFree(C.d_sums);
     hipFree(C.d_trim); hipFree(C.d_tstat);
     C.d_trim = nullptr; C.d_tstat = nullptr;
+    hipFree(C.d_primer); hipFree(C.d_lead); hipFree(C.d_pstat);
+    C.d_primer = nullptr; C.d_lead = nullptr; C.d_pstat = nullptr;
     C.d_text = nullptr; C.d_s0 = C.d_q0 = nullptr;
     C.d_sl = C.d_ql = C.d_tile = C.d_sign = C.d_keep = nullptr;
     C.d_bad = nullptr; C.d_sums = nullptr;
@@ -298,6 +332,101 @@ __global__ __launch_bounds__(256) void k_trim(TrimArgs A)
     }
 }
 
+// ---- k_primer: anchored 5' primers ------------------
+// For a primer p (m bases) and the read r (n bases: the sequence line as
+// k_censor and k_trim left it), D(j) is the unit-cost edit distance between
+// all of p and r[0:j]; (k, j) is a candidate when D(j) <= err[k].  Over the
+// primers of the record's direction the larger m - D wins, then the smaller
+// D, the larger j, the lower primer index, which is the order of the key
+//   (64 - (m - D)) << 21 | D << 15 | (127 - j) << 8 | k
+// (1 <= m - D <= 64 and D < 64 as err < m <= 64; j <= m + err <= 127).
+//
+// One wave per read.  The read's first cols = min(n, largest m + err of the
+// list) bytes sit in two VGPRs, byte j of them is broadcast to every lane
+// through an SGPR each column.  Lane l takes the primers l, l + 64, ...: the
+// column of the DP table over its primer's rows as Myers' vertical delta
+// words (pv, mv), with Hyyro's boundary for a distance from the read's start
+// (the horizontal delta shifted into row 0 is +1: D[0][j] = j, not 0), and
+// the cell of row m followed as a score.  D(j) >= |j - m|, so the columns a
+// lane runs past its own m + err hold no candidate.
+struct PrimerArgs {
+    const uint8_t *text;
+    const int64_t *s0;
+    const int32_t *sign;
+    int64_t n;
+    const int32_t *keep;
+    int32_t *lead;
+    const PrimerTab *tab;
+    unsigned long long *stat;   // [slot] reads, [2 * PRIMER_MAX + slot] bases
+};
+
+__global__ __launch_bounds__(256) void k_primer(PrimerArgs A)
+{
+    constexpr int NS = 2 * PRIMER_MAX;
+    // what this block's reads lost, per slot: a block takes far fewer than
+    // 2^32 / PRIMER_MAXCOL reads
+    __shared__ uint32_t part[2 * NS];
+    for (int i = threadIdx.x; i < 2 * NS; i += blockDim.x) part[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const PrimerTab &T = *A.tab;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < A.n; r += (int64_t)gridDim.x * 4) {
+        const int dir = __builtin_amdgcn_readfirstlane(A.sign[r] == 1 ? 0 : 1);
+        const int n = __builtin_amdgcn_readfirstlane(A.keep[2 * r]);
+        const int np = __builtin_amdgcn_readfirstlane(T.n[dir]);
+        const int cols = min(n, min(__builtin_amdgcn_readfirstlane(T.cols[dir]), PRIMER_MAXCOL));
+        const uint8_t *rd = A.text + A.s0[r];
+        const uint32_t b0 = lane < cols ? (uint32_t)rd[lane] : 0u;
+        const uint32_t b1 = lane + 64 < cols ? (uint32_t)rd[lane + 64] : 0u;
+        uint32_t best = ~0u;
+        for (int k0 = 0; k0 < np && cols > 0; k0 += 64) {
+            const bool act = k0 + lane < np;
+            const int k = act ? k0 + lane : 0;
+            const int m = T.len[dir * PRIMER_MAX + k];
+            const uint64_t eq_a = T.eq[dir][0][k], eq_c = T.eq[dir][1][k];
+            const uint64_t eq_g = T.eq[dir][2][k], eq_t = T.eq[dir][3][k];
+            const uint64_t top = 1ull << (m - 1);
+            uint64_t pv = ~0ull, mv = 0;
+            // lim: the least D so far, from the budget down; at: its last column
+            int score = m, lim = T.err[dir * PRIMER_MAX + k], at = 0;
+            auto column = [&](int j, uint32_t c) {
+                const uint64_t eq = c == 'A' ? eq_a : c == 'C' ? eq_c : c == 'G' ? eq_g : c == 'T' ? eq_t : 0ull;
+                const uint64_t xv = eq | mv;
+                const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
+                uint64_t ph = mv | ~(xh | pv);
+                uint64_t mh = pv & xh;
+                score += (ph & top ? 1 : 0) - (mh & top ? 1 : 0);
+                ph = ph << 1 | 1ull;
+                mh <<= 1;
+                pv = mh | ~(xv | ph);
+                mv = ph & xv;
+                const bool hit = score <= lim;
+                lim = hit ? score : lim;
+                at = hit ? j : at;
+            };
+            const int c0 = min(cols, 64);
+            for (int j = 0; j < c0; ++j) column(j + 1, (uint32_t)__builtin_amdgcn_readlane((int)b0, j));
+            for (int j = 64; j < cols; ++j) column(j + 1, (uint32_t)__builtin_amdgcn_readlane((int)b1, j - 64));
+            if (act && at)
+                best = min(best, (uint32_t)(64 - (m - lim)) << 21 | (uint32_t)lim << 15 |
+                                     (uint32_t)(PRIMER_MAXCOL - at) << 8 | (uint32_t)k);
+        }
+        for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
+        if (lane == 0) {
+            const int j = best == ~0u ? 0 : PRIMER_MAXCOL - (int)(best >> 8 & 127u);
+            A.lead[r] = j;
+            if (j) {
+                const int slot = dir * PRIMER_MAX + (int)(best & 255u);
+                atomicAdd(&part[slot], 1u);
+                atomicAdd(&part[NS + slot], (uint32_t)j);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * NS; i += blockDim.x)
+        if (part[i]) atomicAdd(&A.stat[i], (unsigned long long)part[i]);
+}
+
 
 // ---------------------------------------------------------------------------
 // host
@@ -408,7 +537,11 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     C.base_count = C.score_sum = 0;
     std::fill(std::begin(C.trim_reads), std::end(C.trim_reads), 0);
     std::fill(std::begin(C.trim_bases), std::end(C.trim_bases), 0);
+    std::fill(std::begin(C.primer_reads), std::end(C.primer_reads), 0);
+    std::fill(std::begin(C.primer_bases), std::end(C.primer_bases), 0);
+    C.lead.clear();
     if (nr == 0) return 0;
+    if (C.primer_on) C.lead.assign((size_t)nr, 0);
     // bad-cycle bitmaps per bad tile id, over the cycles of the reads
     int maxc = 1;
     for (int64_t r = 0; r < nr; ++r) maxc = std::max(maxc, std::max(C.sl[r], C.ql[r]));
@@ -435,7 +568,8 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     }
     if (nr > D.cap_rec) {
         hipFree(D.d_s0); hipFree(D.d_q0); hipFree(D.d_sl); hipFree(D.d_ql);
-        hipFree(D.d_tile); hipFree(D.d_sign); hipFree(D.d_keep);
+        hipFree(D.d_tile); hipFree(D.d_sign); hipFree(D.d_keep); hipFree(D.d_lead);
+        D.d_lead = nullptr;
         D.cap_rec = nr;
         H(hipMalloc(&D.d_s0, 8 * nr), "hipMalloc");
         H(hipMalloc(&D.d_q0, 8 * nr), "hipMalloc");
@@ -454,6 +588,10 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     constexpr size_t tstat_bytes = 2 * 2 * TRIM_MAXADAPT * sizeof(unsigned long long);
     if (C.trim_on && !D.d_trim) H(hipMalloc(&D.d_trim, sizeof(TrimTab)), "hipMalloc");
     if (C.trim_on && !D.d_tstat) H(hipMalloc(&D.d_tstat, tstat_bytes), "hipMalloc");
+    constexpr size_t pstat_bytes = 2 * 2 * PRIMER_MAX * sizeof(unsigned long long);
+    if (C.primer_on && !D.d_primer) H(hipMalloc(&D.d_primer, sizeof(PrimerTab)), "hipMalloc");
+    if (C.primer_on && !D.d_pstat) H(hipMalloc(&D.d_pstat, pstat_bytes), "hipMalloc");
+    if (C.primer_on && !D.d_lead) H(hipMalloc(&D.d_lead, 4 * D.cap_rec), "hipMalloc");
     if (st) { censor_free_device(D); return st; }
     H(hipMemcpyAsync(D.d_text, C.text.data(), C.text.size(), hipMemcpyHostToDevice, s), "H2D");
     H(hipMemcpyAsync(D.d_s0, C.s0.data(), 8 * nr, hipMemcpyHostToDevice, s), "H2D");
@@ -487,6 +625,21 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
         }
         H(hipMemcpyAsync(tstat, D.d_tstat, tstat_bytes, hipMemcpyDeviceToHost, s), "D2H");
     }
+    std::vector<unsigned long long> pstat;
+    if (C.primer_on && !st) {   // on what k_censor and k_trim kept
+        pstat.assign(2 * 2 * PRIMER_MAX, 0);
+        H(hipMemcpyAsync(D.d_primer, &C.primer, sizeof(PrimerTab), hipMemcpyHostToDevice, s), "H2D");
+        H(hipMemsetAsync(D.d_pstat, 0, pstat_bytes, s), "memset");
+        PrimerArgs pa{D.d_text, D.d_s0, D.d_sign, nr, D.d_keep, D.d_lead, D.d_primer, D.d_pstat};
+        if (!st) {
+            const int pk = prof_begin(c, "k_primer");
+            hipLaunchKernelGGL(k_primer, dim3((unsigned)blocks), dim3(256), 0, s, pa);
+            prof_end(c, pk);
+            H(hipGetLastError(), "k_primer");
+        }
+        H(hipMemcpyAsync(pstat.data(), D.d_pstat, pstat_bytes, hipMemcpyDeviceToHost, s), "D2H");
+        H(hipMemcpyAsync(C.lead.data(), D.d_lead, 4 * nr, hipMemcpyDeviceToHost, s), "D2H");
+    }
     unsigned long long sums[2] = {0, 0};
     H(hipMemcpyAsync(C.text.data(), D.d_text, C.text.size(), hipMemcpyDeviceToHost, s), "D2H");
     H(hipMemcpyAsync(C.keep.data(), D.d_keep, 8 * nr, hipMemcpyDeviceToHost, s), "D2H");
@@ -515,11 +668,17 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
             C.trim_bases[k] = (int64_t)tstat[2 * TRIM_MAXADAPT + k];
         }
     }
+    if (C.primer_on)
+        for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
+            C.primer_reads[k] = (int64_t)pstat[(size_t)k];
+            C.primer_bases[k] = (int64_t)pstat[(size_t)(2 * PRIMER_MAX + k)];
+        }
     return 0;
 }
 
 // The censored records, rewritten (header and '+' lines verbatim, seq and
-// qual cut to their kept length, each line ending in '\n') and, for gzip,
+// qual from their lead, if primers are set, to their kept length, each line
+// ending in '\n') and, for gzip,
 // deflated, in blocks of records of about CENSOR_BLOCK input bytes, one gzip
 // member per block; the blocks are made by every host thread in turn and
 // placed into C.out by their precomputed offsets.
@@ -554,6 +713,7 @@ static int censor_emit(CensorState &C, int dst_gzip)
     std::atomic<int64_t> next(0);
     std::atomic<int> err(0);
     const char *T = C.text.data();
+    const int32_t *lead = C.lead.empty() ? nullptr : C.lead.data();
     const bool stream = C.sink_fd >= 0;
     // streamed: thread 0 writes the blocks in order as the others finish them
     const int nt = std::max(stream ? 2 : 1, std::min<int>(s2a_threads(), (int)nb + (stream ? 1 : 0)));
@@ -587,11 +747,13 @@ static int censor_emit(CensorState &C, int dst_gzip)
             for (int64_t r = r0; r < r1; ++r) {
                 const size_t hl = (size_t)(C.s0[r] - C.h0[r]), pl = (size_t)(C.q0[r] - C.o0[r]);
                 const size_t ks = (size_t)C.keep[2 * r], kq = (size_t)C.keep[2 * r + 1];
+                // a lead is at most the kept sequence length
+                const size_t ls = lead ? std::min((size_t)lead[r], ks) : 0, lq = std::min(ls, kq);
                 memcpy(o, T + C.h0[r], hl); o += hl;
-                memcpy(o, T + C.s0[r], ks); o += ks;
+                memcpy(o, T + C.s0[r] + ls, ks - ls); o += ks - ls;
                 *o++ = '\n';
                 memcpy(o, T + C.o0[r], pl); o += pl;
-                memcpy(o, T + C.q0[r], kq); o += kq;
+                memcpy(o, T + C.q0[r] + lq, kq - lq); o += kq - lq;
                 *o++ = '\n';
             }
             dst.resize((size_t)(o - dst.data()));
@@ -839,6 +1001,66 @@ extern "C" int mh_censor_trim_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases)
     for (int k = 0; k < 2 * TRIM_MAXADAPT; ++k) {
         reads[k] = c.censor ? c.censor->trim_reads[k] : 0;
         bases[k] = c.censor ? c.censor->trim_bases[k] : 0;
+    }
+    return 0;
+}
+
+extern "C" int mh_censor_set_primers(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                                     const char *const *seqs2, const int32_t *max_errors)
+{
+    if (!ctx) return -3;
+    Ctx &c = *ctx_of(ctx);
+    if (!c.censor) c.censor = new CensorState();
+    CensorState &C = *c.censor;
+    std::fill(std::begin(C.primer_reads), std::end(C.primer_reads), 0);
+    std::fill(std::begin(C.primer_bases), std::end(C.primer_bases), 0);
+    if (n1 == 0 && n2 == 0) { C.primer_on = false; return 0; }
+    if (!max_errors) { set_error("censor: no error table"); return -3; }
+    for (int i = 0; i <= PRIMER_MAXLEN; ++i) {
+        // the fields of k_primer's key: fewer than i errors in i bases, the
+        // last column i + errors within PRIMER_MAXCOL
+        if (max_errors[i] < 0 || max_errors[i] >= std::max(i, 1) || i + max_errors[i] > PRIMER_MAXCOL) {
+            set_error("censor: %d errors allowed in %d primer bases", (int)max_errors[i], i);
+            return -3;
+        }
+    }
+    std::unique_ptr<PrimerTab> T(new PrimerTab());
+    const int n[2] = {n1, n2};
+    const char *const *seqs[2] = {seqs1, seqs2};
+    for (int d = 0; d < 2; ++d) {
+        if (n[d] < 0 || n[d] > PRIMER_MAX || (n[d] && !seqs[d])) {
+            set_error("censor: %d primers for read direction %d (0 to %d)", n[d], d + 1, PRIMER_MAX);
+            return -3;
+        }
+        T->n[d] = n[d];
+        for (int k = 0; k < n[d]; ++k) {
+            const char *p = seqs[d][k];
+            const size_t m = p ? strnlen(p, PRIMER_MAXLEN + 1) : 0;
+            if (m < (size_t)PRIMER_MINLEN || m > (size_t)PRIMER_MAXLEN || strspn(p, "ACGT") != m) {
+                set_error("censor: primer %d of read direction %d (%.70s) is not %d to %d bases of ACGT", k, d + 1,
+                          p ? p : "", PRIMER_MINLEN, PRIMER_MAXLEN);
+                return -3;
+            }
+            const int slot = d * PRIMER_MAX + k;
+            T->len[slot] = (int32_t)m;
+            T->err[slot] = max_errors[m];
+            T->cols[d] = std::max(T->cols[d], (int32_t)m + max_errors[m]);
+            for (size_t i = 0; i < m; ++i)
+                T->eq[d][strchr("ACGT", p[i]) - "ACGT"][k] |= (uint64_t)1 << i;
+        }
+    }
+    C.primer = *T;
+    C.primer_on = true;
+    return 0;
+}
+
+extern "C" int mh_censor_primer_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases)
+{
+    if (!ctx || !reads || !bases) return -3;
+    Ctx &c = *ctx_of(ctx);
+    for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
+        reads[k] = c.censor ? c.censor->primer_reads[k] : 0;
+        bases[k] = c.censor ? c.censor->primer_bases[k] : 0;
     }
     return 0;
 }

@@ -196,6 +196,9 @@ def _declare(L):
         'mh_censor_set_adapters': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, _P], ctypes.c_int),
         'mh_censor_trim_stats': ([_P, _P, _P], ctypes.c_int),
+        'mh_censor_set_primers': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_char_p), _P], ctypes.c_int),
+        'mh_censor_primer_stats': ([_P, _P, _P], ctypes.c_int),
         'mh_a2c_load_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
         'mh_a2c_insert_rows': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, _P, _P, ctypes.c_char_p,
                                 ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)],
@@ -815,6 +818,30 @@ class Context:
         reads, bases = np.zeros(16, dtype=np.int64), np.zeros(16, dtype=np.int64)
         check(lib().mh_censor_trim_stats(self.h, _ptr(reads), _ptr(bases)), 'mh_censor_trim_stats')
         return reads.reshape(2, 8).tolist(), bases.reshape(2, 8).tolist()
+
+    def censor_set_primers(self, primers1, primers2, max_errors):
+        """mh_censor_set_primers: anchored 5' primers (str) of the records of
+        read 1 / of all others for this context's following censor calls,
+        with max_errors[i], i = 0..64, errors allowed in a primer of i bases;
+        two empty lists clear them."""
+        lists = []
+        for primers in (primers1, primers2):
+            lists.append((ctypes.c_char_p * max(len(primers), 1))(*[p.encode() for p in primers]))
+        if len(max_errors) != 65:
+            raise ValueError('max_errors holds {} entries, not 65'.format(len(max_errors)))
+        table = np.array(max_errors, dtype=np.int32)
+        check(lib().mh_censor_set_primers(self.h, len(primers1), lists[0], len(primers2), lists[1],
+                                          _ptr(table)), 'mh_censor_set_primers')
+
+    def censor_clear_primers(self):
+        check(lib().mh_censor_set_primers(self.h, 0, None, 0, None, None), 'mh_censor_set_primers')
+
+    def censor_primer_stats(self):
+        """mh_censor_primer_stats of the last censor call: (reads, bases),
+        each [direction][primer] (2 x 256) with direction 0 = read 1."""
+        reads, bases = np.zeros(512, dtype=np.int64), np.zeros(512, dtype=np.int64)
+        check(lib().mh_censor_primer_stats(self.h, _ptr(reads), _ptr(bases)), 'mh_censor_primer_stats')
+        return reads.reshape(2, 256).tolist(), bases.reshape(2, 256).tolist()
 
     # ---- aln2counts -----------------------------------------------------
     def a2c_load_csv(self, slot, text, codon_chars):
