@@ -237,6 +237,31 @@ int mh_test_set_capacities(mh_ctx *ctx, int64_t cigar_pool_words, int64_t pileup
  *                one, -1 for a reference mh_pileup_only left out
  * ctx may be NULL: the constants alone. */
 int mh_test_pileup_info(mh_ctx *ctx, int64_t *out16, int n_refs, int32_t *win_len);
+/* Test entry point, read-only: the constants that size k_s2a_merge's launch
+ * and the shape of the last one (mh_sam2aln_csv and the other sam2aln calls),
+ * so a test can size its input by them and assert the path it took.
+ *   out16[0..6]  constants: LDS bytes of one block at most (160 KiB), blocks
+ *                of one launch at most (256 * 64), waves per block while they
+ *                fit (4), slots of the grouping table at least (1024),
+ *                q-cutoffs of one call at most, and the bytes a wave keeps in
+ *                LDS per reference position (4) and per CIGAR op (16):
+ *                wave_bytes = 4 * span_cap + 16 * (ops_cap + 1), rounded up
+ *                to 16, span_cap = the longest reference span rounded up to 16
+ *   out16[7..14] the last launch: span_cap, ops_cap, wave_bytes, waves per
+ *                block, blocks, merge units, q-cutoffs, grouping table slots
+ *                (waves per block, blocks and slots 0 for a call refused
+ *                before the launch; all 0 before the first call)
+ *   out16[15]    key_bits as mh_test_set_sam2aln left it
+ * ctx may be NULL: the constants alone. */
+int mh_test_sam2aln_info(mh_ctx *ctx, int64_t *out16);
+/* Test entry point (not a tuning knob), for the sam2aln calls that follow:
+ * key_bits (8..64) = bits of the merged-sequence hash used as the grouping
+ * key, 64 in the product; fewer make distinct sequences share a key, which
+ * the call must report (-4, "hash collision"), never merge.  max_blocks caps
+ * the blocks of k_s2a_merge (0: the library's own cap), so that one wave
+ * merges many units in turn.  The insertion table of mh_sam2aln_conseq_ins
+ * narrows its key the same way.  (64, 0) restores the product's values. */
+int mh_test_set_sam2aln(mh_ctx *ctx, int key_bits, int64_t max_blocks);
 /* Test entry point: on != 0 gives every reference set of later
  * mh_index_build calls the same cache signature, so only the comparison of
  * the cached bytes tells two sets apart. */

@@ -357,6 +357,10 @@ struct TestCaps {
     int64_t pile_event_bytes = 0;   // PileState::ev_pool
     int64_t token_bytes = 0;        // PileState::tok_bytes
     int64_t gotoh_wait_ticks = 0;   // k_gotoh's first-attempt wait limit (0: the default)
+    // mh_test_set_sam2aln: bits of the merged-sequence hash used as the
+    // grouping key (64: all of them) and a cap on k_s2a_merge's blocks (0: none)
+    int s2a_key_bits = 64;
+    int64_t s2a_max_blocks = 0;
 };
 
 // retries taken by the grow-and-retry paths (mh_retry_counts)

@@ -23,6 +23,16 @@ enum { CIG_OK = 0, CIG_STAR = 1, CIG_INVALID = 2, CIG_UNSUPPORTED = 3, CIG_LONG 
 
 constexpr int S2A_MAX_CUTS = 8;  // q-cutoffs of one call (SAM2ALN_Q_CUTOFFS, sam2aln.py:25)
 
+// k_s2a_merge's launch (s2a_run; reported by mh_test_sam2aln_info).  A wave
+// keeps both mates in reference coordinates in LDS: wave_bytes =
+// S2A_SPAN_BYTES * span_cap + S2A_OP_BYTES * (ops_cap + 1), rounded up to 16
+constexpr size_t S2A_LDS_BYTES = 160 * 1024;   // dynamic LDS of one block at most
+constexpr int64_t S2A_BLOCK_CAP = 256 * 64;    // blocks of one launch at most
+constexpr int S2A_WPB = 4;                     // waves per block while they fit in S2A_LDS_BYTES
+constexpr uint64_t S2A_MIN_TABLE = 1024;       // slots of the grouping table at least
+constexpr int S2A_SPAN_BYTES = 4;              // c0 q0 c1 q1: a byte each per reference position
+constexpr int S2A_OP_BYTES = 16;               // reference and read offset (int32) per op and mate
+
 struct S2AShard;                 // sam2aln split over the ranks of a job (mh_s2a_shard.cpp)
 void s2a_shard_free(S2AShard *sh);
 
@@ -157,6 +167,13 @@ struct S2AState {
     double t_parse = 0, t_device = 0, t_format[3] = {0, 0, 0};
     S2AClip clip;
     S2AIns ins;
+    // shape of the last k_s2a_merge launch, kept for mh_test_sam2aln_info
+    // (host bookkeeping; nothing reads it otherwise).  wpb and blocks stay 0
+    // when the call was refused before the launch
+    struct Info {
+        int span_cap = 0, ops_cap = 0, wave_bytes = 0, wpb = 0, n_cut = 0;
+        int64_t blocks = 0, n_merge = 0, tsize = 0;
+    } info;
     // ---- this rank's part of a sharded sam2aln ----
     S2AShard *shard = nullptr;
     ~S2AState() { if (shard) s2a_shard_free(shard); }

@@ -414,16 +414,23 @@ __global__ __launch_bounds__(256) void k_s2a_merge(S2AArgs A)
     }
 }
 
-__device__ __forceinline__ uint64_t s2a_key(uint64_t h1) { return h1 ? h1 : 1ull; }
+// the grouping key of a hash: the hash itself (never 0) in the product; a
+// test narrows it to key_bits < 64 bits (mh_test_set_sam2aln), shifted and
+// made odd as k_a2c_var_hash does, so that distinct sequences share keys
+__device__ __forceinline__ uint64_t s2a_key(uint64_t h1, int key_bits = 64)
+{
+    if (key_bits >= 64) return h1 ? h1 : 1ull;
+    return ((h1 & ((1ull << key_bits) - 1)) << 1) | 1ull;
+}
 
 __global__ __launch_bounds__(256) void k_s2a_count(const int32_t *res, const uint64_t *h, int64_t n,
                                                    uint64_t *tkey, int32_t *tcnt, int32_t *trep,
-                                                   uint64_t mask)
+                                                   uint64_t mask, int key_bits)
 {
     for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n;
          u += (int64_t)gridDim.x * blockDim.x) {
         if (res[4 * u] != S2A_OK) continue;
-        const uint64_t key = s2a_key(h[2 * u]);
+        const uint64_t key = s2a_key(h[2 * u], key_bits);
         const uint64_t s = table_claim(tkey, mask, key & mask, key).slot;
         atomicAdd(&tcnt[s], 1);
         atomicMin(&trep[s], (int32_t)u);
@@ -434,14 +441,14 @@ __global__ __launch_bounds__(256) void k_s2a_verify(const int32_t *res, const ui
                                                     const int32_t *uref, const int64_t *slot,
                                                     const uint8_t *out, int64_t n, int n_cut,
                                                     const uint64_t *tkey, const int32_t *trep,
-                                                    uint64_t mask, int32_t *ctr)
+                                                    uint64_t mask, int32_t *ctr, int key_bits)
 {
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
     for (int64_t u = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); u < n;
          u += (int64_t)gridDim.x * wpb) {
         if (res[4 * u] != S2A_OK) continue;
-        const uint64_t key = s2a_key(h[2 * u]);
+        const uint64_t key = s2a_key(h[2 * u], key_bits);
         const int64_t r = trep[table_find(tkey, mask, key & mask, key)];
         if (r == u) continue;
         // same group: same rname and same cutoff (entry = unit * n_cut + k)
@@ -698,10 +705,16 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
         return -3;
     }
     span_cap = (span_cap + 15) & ~15;
-    const int wave_bytes = ((4 * span_cap + 2 * 4 * 2 * (ops_cap + 1)) + 15) & ~15;
-    int wpb = 4;
-    while (wpb > 1 && (size_t)wpb * wave_bytes > 160 * 1024) --wpb;
-    if ((size_t)wave_bytes > 160 * 1024) {
+    const int wave_bytes = ((S2A_SPAN_BYTES * span_cap + S2A_OP_BYTES * (ops_cap + 1)) + 15) & ~15;
+    int wpb = S2A_WPB;
+    while (wpb > 1 && (size_t)wpb * wave_bytes > S2A_LDS_BYTES) --wpb;
+    S.info = S2AState::Info();
+    S.info.span_cap = span_cap;
+    S.info.ops_cap = ops_cap;
+    S.info.wave_bytes = wave_bytes;
+    S.info.n_merge = S.n_merge;
+    S.info.n_cut = nc;
+    if ((size_t)wave_bytes > S2A_LDS_BYTES) {
         set_error("sam2aln: reference span %d too long for LDS", span_cap);
         return -3;
     }
@@ -719,7 +732,7 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
     if (int st = s2a_upload(S, S.d_uref, mref, s)) return st;
     if (int st = s2a_upload(S, S.d_slot, slot, s)) return st;
     const int64_t nm = S.n_merge, ne = nm * nc;   // pairs, entries
-    uint64_t tsize = 1024;
+    uint64_t tsize = S2A_MIN_TABLE;
     while (tsize < (uint64_t)(2 * ne)) tsize <<= 1;
     if (int st = dev_reserve(S, S.d_out, total > 0 ? (size_t)total : 1)) return st;
     if (int st = dev_reserve(S, S.d_res, sizeof(int32_t) * 4 * ne)) return st;
@@ -741,7 +754,15 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
               wave_bytes, S.d_out, S.d_res, S.d_h, S.d_ctr};
     for (int k = 0; k < nc; ++k) a.cut[k] = (unsigned char)(S.q_cutoffs[k] + 33);
     int64_t blocks = (nm + wpb - 1) / wpb;
-    if (blocks > 256 * 64) blocks = 256 * 64;
+    if (blocks > S2A_BLOCK_CAP) blocks = S2A_BLOCK_CAP;
+    // mh_test_set_sam2aln: fewer blocks (a wave then takes several units in
+    // turn) and a narrowed grouping key; 0 and 64 in the product
+    const int64_t max_blocks = c.test_caps.s2a_max_blocks;
+    const int key_bits = c.test_caps.s2a_key_bits;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    S.info.wpb = wpb;
+    S.info.blocks = blocks;
+    S.info.tsize = (int64_t)tsize;
     // the instance whose compile-time bound is the next power of two >= nc
     void (*merge)(S2AArgs) = nc == 1 ? k_s2a_merge<1> : nc == 2 ? k_s2a_merge<2>
                              : nc <= 4 ? k_s2a_merge<4> : k_s2a_merge<8>;
@@ -755,11 +776,11 @@ int s2a_run(Ctx &c, S2AState &S, double max_prop_n, const S2ADevRows *dev)
     if (tb > 65536) tb = 65536;
     const int p1 = prof_begin(c, "k_s2a_group");
     hipLaunchKernelGGL(k_s2a_count, dim3((unsigned)tb), dim3(256), 0, s, S.d_res, S.d_h, ne,
-                       S.d_tkey, S.d_tcnt, S.d_trep, tsize - 1);
+                       S.d_tkey, S.d_tcnt, S.d_trep, tsize - 1, key_bits);
     int64_t vb = (ne + 3) / 4;
     if (vb > 256 * 64) vb = 256 * 64;
     hipLaunchKernelGGL(k_s2a_verify, dim3((unsigned)vb), dim3(256), 0, s, S.d_res, S.d_h, S.d_uref,
-                       S.d_slot, S.d_out, ne, nc, S.d_tkey, S.d_trep, tsize - 1, S.d_ctr);
+                       S.d_slot, S.d_out, ne, nc, S.d_tkey, S.d_trep, tsize - 1, S.d_ctr, key_bits);
     int64_t cb = (int64_t)((tsize + 255) / 256);
     if (cb > 65536) cb = 65536;
     hipLaunchKernelGGL(k_s2a_compact, dim3((unsigned)cb), dim3(256), 0, s, S.d_tkey, S.d_tcnt,
@@ -1420,13 +1441,13 @@ constexpr int INS_COMBINE = 4;
 
 __global__ __launch_bounds__(256) void k_s2a_ins_tab(const int32_t *res, const uint64_t *h, int64_t n,
                                                      uint64_t *tkey, int32_t *tcnt, int32_t *trep,
-                                                     uint64_t mask, int combine)
+                                                     uint64_t mask, int combine, int key_bits)
 {
     const int lane = threadIdx.x & 63;
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t key = 0;
     bool todo = false;
-    if (e < n && res[4 * e] == S2A_OK) { key = s2a_key(h[2 * e]); todo = true; }
+    if (e < n && res[4 * e] == S2A_OK) { key = s2a_key(h[2 * e], key_bits); todo = true; }
     for (int round = 0; combine && round < INS_COMBINE; ++round) {
         const unsigned long long act = __ballot(todo);
         if (!act) break;
@@ -1561,16 +1582,17 @@ int s2a_ins_run(Ctx &c, S2AState &S)
     MH_HIP(hipGetLastError());
     static const bool combine = !(getenv("MICALL_INS_COMBINE") && *getenv("MICALL_INS_COMBINE") == '0');
     const int64_t tb = (ne + 255) / 256;     // a thread per entry: ne <= 0x7f7f7f7f
+    const int key_bits = c.test_caps.s2a_key_bits;   // mh_test_set_sam2aln; 64 in the product
     const int p2 = prof_begin(c, "k_s2a_ins_tab");
     hipLaunchKernelGGL(k_s2a_ins_tab, dim3((unsigned)tb), dim3(256), 0, s, I.d_res, I.d_h, ne, I.d_tkey,
-                       I.d_tcnt, I.d_trep, tsize - 1, combine ? 1 : 0);
+                       I.d_tcnt, I.d_trep, tsize - 1, combine ? 1 : 0, key_bits);
     prof_end(c, p2);
     MH_HIP(hipGetLastError());
     int64_t vb = (ne + 3) / 4;
     if (vb > 256 * 64) vb = 256 * 64;
     const int p3 = prof_begin(c, "k_s2a_ins_group");
     hipLaunchKernelGGL(k_s2a_verify, dim3((unsigned)vb), dim3(256), 0, s, I.d_res, I.d_h, I.d_rref,
-                       I.d_slot, I.d_out, ne, nc, I.d_tkey, I.d_trep, tsize - 1, I.d_ctr);
+                       I.d_slot, I.d_out, ne, nc, I.d_tkey, I.d_trep, tsize - 1, I.d_ctr, key_bits);
     int64_t cb = (int64_t)((tsize + 255) / 256);
     if (cb > 65536) cb = 65536;
     hipLaunchKernelGGL(k_s2a_compact, dim3((unsigned)cb), dim3(256), 0, s, I.d_tkey, I.d_tcnt, I.d_trep,
@@ -2134,6 +2156,40 @@ extern "C" int mh_sam2aln_timing(mh_ctx *ctx, double *ms5)
     ms5[0] = S.t_parse;
     ms5[1] = S.t_device;
     for (int k = 0; k < 3; ++k) ms5[2 + k] = S.t_format[k];
+    return 0;
+}
+
+extern "C" int mh_test_sam2aln_info(mh_ctx *ctx, int64_t *out16)
+{
+    if (!out16) { set_error("mh_test_sam2aln_info: no output array"); return -3; }
+    const int64_t consts[7] = {S2A_LDS_BYTES, S2A_BLOCK_CAP, S2A_WPB, S2A_MIN_TABLE, S2A_MAX_CUTS,
+                               S2A_SPAN_BYTES, S2A_OP_BYTES};
+    for (int k = 0; k < 16; ++k) out16[k] = k < 7 ? consts[k] : 0;
+    if (!ctx) return 0;
+    const Ctx &c = *ctx_of(ctx);
+    out16[15] = c.test_caps.s2a_key_bits;
+    if (!c.s2a) return 0;
+    const S2AState::Info &I = c.s2a->info;
+    out16[7] = I.span_cap;
+    out16[8] = I.ops_cap;
+    out16[9] = I.wave_bytes;
+    out16[10] = I.wpb;
+    out16[11] = I.blocks;
+    out16[12] = I.n_merge;
+    out16[13] = I.n_cut;
+    out16[14] = I.tsize;
+    return 0;
+}
+
+extern "C" int mh_test_set_sam2aln(mh_ctx *ctx, int key_bits, int64_t max_blocks)
+{
+    if (!ctx || key_bits < 8 || key_bits > 64 || max_blocks < 0) {
+        set_error("mh_test_set_sam2aln: key_bits outside 8..64 or max_blocks < 0");
+        return -3;
+    }
+    TestCaps &t = ctx_of(ctx)->test_caps;
+    t.s2a_key_bits = key_bits;
+    t.s2a_max_blocks = max_blocks;
     return 0;
 }
 

@@ -83,6 +83,8 @@ def _declare(L):
         'mh_test_set_capacities': ([_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64], ctypes.c_int),
         'mh_test_pileup_info': ([_P, _P, ctypes.c_int, _P], ctypes.c_int),
+        'mh_test_sam2aln_info': ([_P, _P], ctypes.c_int),
+        'mh_test_set_sam2aln': ([_P, ctypes.c_int, ctypes.c_int64], ctypes.c_int),
         'mh_test_force_index_collision': ([_P, ctypes.c_int], ctypes.c_int),
         'mh_retry_counts': ([_P, _P], ctypes.c_int),
         'mh_test_set_gotoh_wait': ([_P, ctypes.c_int64], ctypes.c_int),
@@ -346,6 +348,11 @@ PILEUP_INFO_FIELDS = ('xch_span', 'max_ops', 'ins_buf', 'max_ins', 'tok_lds_slot
                       'tok_count_blocks', 'tok_events', 'tok_keys', 'n_refs')
 
 
+# mh_test_sam2aln_info: seven constants, the last k_s2a_merge launch, key_bits
+SAM2ALN_INFO_FIELDS = ('lds_bytes', 'block_cap', 'wpb_max', 'min_table', 'max_cuts', 'span_bytes',
+                       'op_bytes', 'span_cap', 'ops_cap', 'wave_bytes', 'wpb', 'blocks', 'n_merge',
+                       'n_cut', 'tsize', 'key_bits')
+
 WATCH_MAXKEYS, WATCH_QBINS, WATCH_Q0 = 1024, 95, 32
 WATCH_NEVER = np.iinfo(np.int64).max
 
@@ -427,6 +434,14 @@ def pileup_info(handle=None, n_refs=0):
     info = dict(zip(PILEUP_INFO_FIELDS, (int(x) for x in out)))
     info['win_len'] = win[:n_refs].tolist()
     return info
+
+
+def sam2aln_info(handle=None):
+    """mh_test_sam2aln_info: dict of SAM2ALN_INFO_FIELDS.  Without a context
+    handle only the library's constants are set (needs no GPU)."""
+    out = np.zeros(16, dtype=np.int64)
+    check(lib().mh_test_sam2aln_info(handle, _ptr(out)), 'mh_test_sam2aln_info')
+    return dict(zip(SAM2ALN_INFO_FIELDS, (int(x) for x in out)))
 
 
 def params(mode, rdg=(10, 3), rfg=(10, 3), maxins=1200):
@@ -1299,6 +1314,17 @@ class Context:
         n = ctypes.c_int()
         check(lib().mh_pileup_dims(self.h, ctypes.byref(n), None, None, None), 'mh_pileup_dims')
         return pileup_info(self.h, n.value)
+
+    def test_sam2aln_info(self):
+        """Test entry point: shape of the last k_s2a_merge launch and the
+        constants that size it (sam2aln_info)."""
+        return sam2aln_info(self.h)
+
+    def test_set_sam2aln(self, key_bits=64, max_blocks=0):
+        """Test entry point: the later sam2aln calls group on key_bits
+        (8..64) bits of the hash and launch at most max_blocks merge blocks
+        (0: the library's cap); the defaults are the product's values."""
+        check(lib().mh_test_set_sam2aln(self.h, int(key_bits), int(max_blocks)), 'mh_test_set_sam2aln')
 
     def test_force_index_collision(self, on=True):
         """Test entry point: every later index_build gets the same cache

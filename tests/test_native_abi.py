@@ -56,6 +56,26 @@ def test_pileup_info_constants_without_context(native):
         native.check(native.lib().mh_test_pileup_info(None, None, 0, None), 'mh_test_pileup_info')
 
 
+def test_sam2aln_info_constants_without_context(native):
+    """mh_test_sam2aln_info with no context: the constants that size
+    k_s2a_merge's launch (what tests/s2a_merge_cases.py sizes its cases by),
+    no launch shape; mh_test_set_sam2aln needs a context."""
+    info = native.sam2aln_info()
+    assert list(info) == list(native.SAM2ALN_INFO_FIELDS) and len(info) == 16
+    # DESIGN section 6: 160 KiB of LDS, four waves a block while they fit
+    assert info['lds_bytes'] == 160 * 1024 and info['wpb_max'] == 4
+    assert info['block_cap'] == 256 * 64 and info['min_table'] == 1024
+    assert info['max_cuts'] == 8
+    # c0 q0 c1 q1 per position; reference and read offset (int32) per op and mate
+    assert info['span_bytes'] == 4 and info['op_bytes'] == 2 * 2 * 4
+    assert all(info[k] == 0 for k in native.SAM2ALN_INFO_FIELDS[7:])
+    with pytest.raises(native.NativeError):
+        native.check(native.lib().mh_test_sam2aln_info(None, None), 'mh_test_sam2aln_info')
+    for bits, blocks in ((64, 0), (8, 1)):
+        with pytest.raises(native.NativeError, match='mh_test_set_sam2aln'):
+            native.check(native.lib().mh_test_set_sam2aln(None, bits, blocks), 'mh_test_set_sam2aln')
+
+
 def test_no_cpu_fallback_without_gpu(native):
     """On a host without a GPU the context refuses to start (no fallback)."""
     if native.device_count() > 0:
