@@ -210,8 +210,15 @@ int mh_map_counts(mh_ctx *ctx, int64_t *lines, int64_t *filtered, int64_t *mappe
  * (candidates aligned by the DP, up to 31 diagonals x read length cells each,
  * mate rescues included), out[2] CIGAR pool words reserved (per-wave
  * chunks), out[3] extensions resolved by the ungapped fast path (no DP),
- * out[4] mate-rescue extensions. */
+ * out[4] mate-rescue candidates found.  A rescue candidate on a (strand,
+ * reference, diagonal) the main pass already extended for that mate, and
+ * failed on, is not extended again: it counts in out[4] but not in out[1]. */
 int mh_map_stats(mh_ctx *ctx, int64_t *out5);
+/* Test entry point: *out = the mate-rescue candidates of the last mh_map that
+ * were not extended again (see mh_map_stats; out[4] - *out ran through the
+ * DP).  The caller's five-value buffer of mh_map_stats cannot grow, hence
+ * the separate call. */
+int mh_test_rescue_skipped(mh_ctx *ctx, int64_t *out);
 /* Test entry point (not a tuning knob): start the grow-and-retry buffers of
  * every later call at these capacities (0 = the library's own sizing):
  * the CIGAR pool of mh_map (uint32 words), the pileup's insertion-token

@@ -1303,6 +1303,15 @@ int mh_map_stats(mh_ctx *ctx, int64_t *out5)
     return 0;
 }
 
+int mh_test_rescue_skipped(mh_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return -3;
+    MapState &M = X(ctx)->map;
+    if (!M.valid) { set_error("no mapping results (call mh_map)"); return -3; }
+    *out = M.last_rescue_skipped;
+    return 0;
+}
+
 int mh_test_force_index_collision(mh_ctx *ctx, int on)
 {
     if (!ctx) return -3;

@@ -182,14 +182,15 @@ struct MapState {
     int64_t pool_cap = 0;
     unsigned long long *pool_used = nullptr;  // words claimed (demand; may exceed pool_cap)
     Rec *rec = nullptr;          // n_reads
-    int32_t *counters = nullptr; // [work_n, unused, pool_overflow, fast, rescue_n, queue, rescue queue, pad]
+    int32_t *counters = nullptr; // [work_n, unused, pool_overflow, fast, rescue_n, queue, rescue queue, rescue skipped]
     int64_t *ref_stats = nullptr;// per ref: lines, filtered, mapped, first_row, first_mapped; + unmapped, star
     int64_t cap_reads = 0;
     int cap_refs = 0;
     int64_t last_work = 0;       // extensions (k_dp work items) of the last pass
     int64_t last_cigar = 0;      // CIGAR ops written by the last pass
     int64_t last_fast = 0;       // extensions resolved by the ungapped fast path
-    int64_t last_rescue = 0;     // mate-rescue extensions
+    int64_t last_rescue = 0;     // mate-rescue candidates found (extended or skipped)
+    int64_t last_rescue_skipped = 0;  // of those, not extended: the main pass had failed on the same diagonal
     bool valid = false;
     // host copy of ref_stats (5 * n_refs + 3), filled on first use after a
     // mapping pass: mh_map_counts and the pileup's window choice share it

@@ -15,7 +15,8 @@
 //                 traceback -> CIGAR; an exact ungapped fast path first
 //   k_rescue      paired reads with one aligned mate: the other mate's best
 //                 diagonal in the -X window next to it (mate rescue), then
-//                 k_dp again over those candidates
+//                 k_dp again over those candidates (but for a diagonal the
+//                 main pass already extended for that mate, and failed on)
 //   k_pair        one thread per pair: concordance, flags, MAPQ, SAM fields,
 //                 per-reference line tallies
 #include <cstring>
@@ -2127,9 +2128,13 @@ __global__ __launch_bounds__(256) void k_dp(DpArgs A)
 // exactly one mate of a pair aligned, the other is looked for in the -X
 // window next to the aligned mate, on the opposite strand: the diagonal with
 // the most base matches over the window (ties: leftmost) becomes the mate's
-// only candidate and k_dp extends it like any other.  One wave per 64 pairs:
-// lane = pair for the test, then the whole wave scans each selected mate's
-// window, lane = diagonal, 4 read bases per LDS word.
+// only candidate and k_dp extends it like any other -- unless it is one of
+// the mate's main-pass candidates (same strand, reference and centre): that
+// extension has run and failed, the mate is left as it is and only counted.
+// One wave per 64 pairs: lane = pair for the test, then the whole wave scans
+// each selected mate's window: 16 consecutive diagonals per lane from
+// registers (reads of <= 256 nt without ambiguous bases), else lane =
+// diagonal, 32 or 16 bases per LDS word.
 // ---------------------------------------------------------------------------
 struct RescueArgs {
     DevReads R;
@@ -2139,7 +2144,7 @@ struct RescueArgs {
     const int32_t *yf;
     Cand *cand;
     int32_t *work;        // rescue work list (slot ids)
-    int32_t *counter;     // [0] rescue work items
+    int32_t *counter;     // [0] rescue work items, [3] mates skipped (diagonal already extended)
     int maxins;
     int64_t plane;        // slot planes' stride (slot_at)
 };
@@ -2169,7 +2174,48 @@ __device__ __forceinline__ int best_slot(const SlotKey *skey, int64_t r, int n, 
     return best;
 }
 
-__global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
+// The count without ambiguous bases for reads of NW bit-plane words, register
+// blocked: the lane takes the 16 consecutive diagonals from t = 16 lane on.
+// They share the window words pl[lane >> 1 .. + NW] (held in registers) and
+// differ in the funnel shift only; the read's words are the same for every
+// lane (scalar registers).  No LDS access inside the shift loop.  A lane keeps
+// its first maximum in increasing d, as the strided loop does.
+template <int NW>
+__device__ __forceinline__ void rescue_scan16(const uint2 *pl, const uint2 *rp, int lane, int nd, int d0,
+                                              int m, uint32_t tmask, int &bestM, int &bestd)
+{
+    uint32_t r0[NW], r1[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const uint2 r = rp[i];
+        r0[i] = __builtin_amdgcn_readfirstlane(r.x);
+        r1[i] = __builtin_amdgcn_readfirstlane(r.y);
+    }
+    const int t0 = 16 * lane;
+    if (t0 >= nd) return;
+    const int w0 = lane >> 1;   // t >> 5 of the whole block
+    uint2 W[NW + 1];
+#pragma unroll
+    for (int i = 0; i <= NW; ++i) W[i] = pl[w0 + i];
+    uint32_t sh = (uint32_t)(t0 & 31);   // 0 or 16: the 16 shifts stay below 32
+#pragma unroll 1
+    for (int k = 0; k < 16; ++k, ++sh) {
+        int mis = 0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const uint32_t x0 = __builtin_amdgcn_alignbit(W[i + 1].x, W[i].x, sh) ^ r0[i];
+            const uint32_t x1 = __builtin_amdgcn_alignbit(W[i + 1].y, W[i].y, sh) ^ r1[i];
+            mis += __builtin_popcount(i == NW - 1 ? (x0 | x1) & tmask : x0 | x1);
+        }
+        const int cnt = m - mis;
+        if (t0 + k < nd && cnt > bestM) { bestM = cnt; bestd = d0 + t0 + k; }
+    }
+}
+
+// The blocked scan holds 18 window words per lane: built for 5 waves per SIMD
+// (91 VGPRs, no scratch; left to itself the compiler takes 100 and 4 waves).
+constexpr int RESCUE_WAVES_PER_SIMD = 5;
+__global__ __launch_bounds__(256, RESCUE_WAVES_PER_SIMD) void k_rescue(RescueArgs A)
 {
     // the mate and the reference window as 2-bit words (16 bases each) plus
     // "N" masks (01 in the base's bit pair)
@@ -2212,7 +2258,7 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
             }
         }
         uint64_t todo = __builtin_amdgcn_ballot_w64(need != 0);
-        int n_items = 0;
+        int n_items = 0, n_skip = 0;
         while (todo) {
             const int l = __builtin_ctzll(todo);
             todo &= todo - 1;
@@ -2231,6 +2277,15 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
             if (hi > reflen) hi = reflen;
             if (hi - lo < m) continue;
             const int s = 1 - ast;
+            // the mate's own candidates, all extended by the main pass and all
+            // failed (lane = candidate, the planes past n_cand hold no candidate;
+            // compared once the diagonal is known)
+            Cand mine{-1, -1, 0, 0};
+            int tnc = 0;
+            if (lane < MAXCAND) {
+                mine = A.cand[(int64_t)lane * A.plane + tg];
+                tnc = A.n_cand[tg];
+            }
             // the mate on strand s; bases past its end count as N (never match)
             const int nw = (m + 15) >> 4;
             bool read_n = false;   // an ambiguous base inside the read
@@ -2281,7 +2336,18 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
                     // no ambiguous base on either side: mismatches over 32 bases
                     // per step from the two planes (the window's words aligned to
                     // the diagonal by a funnel shift, carried over a step); the
-                    // last word masks the read's tail
+                    // last word masks the read's tail.  Reads of up to 8
+                    // words (256 nt) take the register-blocked scan.
+                    switch (nw32) {
+                    case 1: rescue_scan16<1>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 2: rescue_scan16<2>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 3: rescue_scan16<3>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 4: rescue_scan16<4>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 5: rescue_scan16<5>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 6: rescue_scan16<6>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 7: rescue_scan16<7>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    case 8: rescue_scan16<8>(pl, rp, lane, nd, d0, m, tmask, bestM, bestd); break;
+                    default:
                     for (int t = lane; t < nd; t += 64) {
                         const int w0 = t >> 5;
                         const uint32_t sh = (uint32_t)(t & 31);
@@ -2302,6 +2368,7 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
                         }
                         const int cnt = m - mis;
                         if (cnt > bestM) { bestM = cnt; bestd = d0 + t; }
+                    }
                     }
                     wave_sync();
                     continue;
@@ -2347,6 +2414,14 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
             }
             const int mmax = wave_max(bestM);
             const int dsel = wave_min(bestM == mmax ? bestd : INT32_MAX);
+            // dp_extend is a function of (read, strand, reference, centre): a
+            // diagonal the main pass extended for this mate has failed already.
+            // Such a mate stays as it is, every slot invalid, like a mate whose
+            // rescue fails.
+            if (__builtin_amdgcn_ballot_w64(lane < tnc && mine.strand == s && mine.ref == ref && mine.center == dsel) != 0) {
+                ++n_skip;
+                continue;
+            }
             if (lane == 0) {
                 A.cand[tg] = Cand{s, ref, dsel, 0};   // candidate 0: plane 0
                 A.n_cand[tg] = 1;
@@ -2361,6 +2436,7 @@ __global__ __launch_bounds__(256) void k_rescue(RescueArgs A)
             base = __builtin_amdgcn_readfirstlane(base);
             if (lane < n_items) A.work[base + lane] = sh_items[wv][lane];
         }
+        if (lane == 0 && n_skip) atomicAdd(A.counter + 3, n_skip);
         wave_sync();
     }
 }
@@ -2957,7 +3033,8 @@ int run_map(Ctx &c, const mh_params &par)
         if (pblocks < 1) pblocks = 1;
         for (int attempt = 0; attempt < 2; ++attempt) {
             // counters: [0] work items, [2] pool overflow, [3] fast path,
-            // [4] rescue work items; pool_used: CIGAR words claimed.  The
+            // [4] rescue work items, [7] rescue candidates not extended again;
+            // pool_used: CIGAR words claimed.  The
             // pairing runs before the overflow check (it reads the slots,
             // not the pool; a retry starts the tallies again), so a pass
             // synchronises once.
@@ -2982,13 +3059,14 @@ int run_map(Ctx &c, const mh_params &par)
             hipLaunchKernelGGL(k_pair, dim3((unsigned)pblocks), dim3(256), 0, s, pa);
             prof_end(c, pp);
             MH_HIP(hipGetLastError());
-            int32_t ctr[5];
+            int32_t ctr[8];
             unsigned long long used = 0;
             MH_HIP(hipMemcpyAsync(ctr, M.counters, sizeof(ctr), hipMemcpyDeviceToHost, s));
             MH_HIP(hipMemcpyAsync(&used, M.pool_used, sizeof(used), hipMemcpyDeviceToHost, s));
             MH_HIP(hipStreamSynchronize(s));
             M.last_work = ctr[0] + ctr[4];
-            M.last_rescue = ctr[4];
+            M.last_rescue = ctr[4] + ctr[7];
+            M.last_rescue_skipped = ctr[7];
             M.last_cigar = (int64_t)used;
             M.last_fast = ctr[3];
             if (!ctr[2]) break;

@@ -77,6 +77,7 @@ def _declare(L):
         'mh_alns_fetch': ([_P, ctypes.c_int64, ctypes.c_int64, _P], ctypes.c_int),
         'mh_map_counts': ([_P, _P, _P, _P, _P, _P, _I64P, _I64P, _I64P], ctypes.c_int),
         'mh_map_stats': ([_P, _P], ctypes.c_int),
+        'mh_test_rescue_skipped': ([_P, _I64P], ctypes.c_int),
         'mh_recs_fetch_fields': ([_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P],
                                  ctypes.c_int),
         'mh_recs_fetch': ([_P, ctypes.c_int64, ctypes.c_int64, _P], ctypes.c_int),
@@ -1287,6 +1288,14 @@ class Context:
         out = np.zeros(5, dtype=np.int64)
         check(lib().mh_map_stats(self.h, _ptr(out)), 'mh_map_stats')
         return tuple(int(x) for x in out)
+
+    def rescue_skipped(self):
+        """Mate-rescue candidates of the last mapping pass that were not
+        extended again (the main pass had failed on the same diagonal); they
+        count in map_stats()[4], not in map_stats()[1]."""
+        out = ctypes.c_int64(0)
+        check(lib().mh_test_rescue_skipped(self.h, ctypes.byref(out)), 'mh_test_rescue_skipped')
+        return int(out.value)
 
     def probe_extend(self, par, items):
         """Diagnostics: items = (n, 4) int32 (read, strand, ref, centre) of

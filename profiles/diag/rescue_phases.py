@@ -32,9 +32,9 @@ def main():
     open(os.path.join(DST, 'Makefile'), 'w').write(mk)
     p = os.path.join(DST, 'mh_map.hip')
     t = open(p).read()
-    t = sub(t, '__global__ __launch_bounds__(256) void k_rescue(RescueArgs A)\n{\n',
+    t = sub(t, '__global__ __launch_bounds__(256, RESCUE_WAVES_PER_SIMD) void k_rescue(RescueArgs A)\n{\n',
             '__device__ unsigned long long g_rph[8];\n'
-            '__global__ __launch_bounds__(256) void k_rescue(RescueArgs A)\n{\n'
+            '__global__ __launch_bounds__(256, RESCUE_WAVES_PER_SIMD) void k_rescue(RescueArgs A)\n{\n'
             '    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};\n'
             '    unsigned long long t0 = __builtin_readcyclecounter(), t1;\n'
             '#define RPH(k) do { wave_sync(); t1 = __builtin_readcyclecounter(); ph[k] += t1 - t0; t0 = t1; } while (0)\n')
@@ -47,8 +47,8 @@ def main():
             '                RPH(2);\n')
     t = sub(t, '            const int mmax = wave_max(bestM);\n',
             '            RPH(3);\n            const int mmax = wave_max(bestM);\n')
-    t = sub(t, '            if (lane < n_items) A.work[base + lane] = sh_items[wv][lane];\n        }\n        wave_sync();\n    }\n}',
-            '            if (lane < n_items) A.work[base + lane] = sh_items[wv][lane];\n        }\n        wave_sync();\n'
+    t = sub(t, '        if (lane == 0 && n_skip) atomicAdd(A.counter + 3, n_skip);\n        wave_sync();\n    }\n}',
+            '        if (lane == 0 && n_skip) atomicAdd(A.counter + 3, n_skip);\n        wave_sync();\n'
             '        RPH(4);\n    }\n'
             '    if (lane == 0) for (int k = 0; k < 8; ++k) atomicAdd(&g_rph[k], ph[k]);\n}')
     t = sub(t, '                if (int st = launch_dp(M.rwork, M.counters + 4,',
