@@ -42,7 +42,9 @@
  *          -> mh_a2c_load_csv / mh_a2c_load_rows, mh_a2c_counts,
  *             mh_a2c_inserts; the nucleotide variants of the coordinate
  *             regions (:346-375, :537-549) -> mh_a2c_variants; the codons
- *             count_aminos drops (:595-603) -> mh_a2c_codon_detail.
+ *             count_aminos drops (:595-603) -> mh_a2c_codon_detail; the
+ *             amino acids one read links at chosen positions (no
+ *             counterpart in the reference) -> mh_a2c_link.
  *
  * Conventions: every function returns 0 on success, -1 on traceback failure
  * (mh_gotoh_align only), -2 on out-of-memory, -3 on a bad argument, -4 on a
@@ -841,6 +843,40 @@ int mh_a2c_variant_entries(mh_ctx *ctx, int slot, int32_t *region, int64_t *coun
  * left some of them out, bytes of sequence text copied to the host; *ms (may
  * be NULL) = host wall ms of the call, device work included. */
 int mh_a2c_variant_stats(mh_ctx *ctx, int slot, int64_t *stats4, double *ms);
+/* Linked amino acids (not in the reference): n_sets sets of consensus codons
+ * over the rows of group g.  Set s holds the codons codon[set_first[s] ..
+ * set_first[s + 1]) (1 to 12 of them, 0-based, in the order of the haplotype)
+ * and is read in reading frame frame[s] (0..2); set_first[0] = 0.  A row's
+ * codon at k is the bytes at read indices 3k - frame - offset + 0..2, '-'
+ * outside the row, and its character is the class mh_a2c_counts /
+ * mh_a2c_codon_detail count it in: one of the 21 letters, 'X', '?' (partial),
+ * '-' (del).  A row counts for a set when none of the set's codons is blank
+ * (padding only, or only the gap between the mates); its haplotype is the
+ * set's characters, and equal haplotypes of a set add their counts up
+ * (64-bit).  The grouping key is the haplotype itself (5 bits a codon, the
+ * set's index within a pass of at most 16 sets and 64 codons in the top four
+ * bits; further sets go in further passes), so there is no collision to
+ * report.  Only entries with count >= min_count leave the device, as
+ * fixed-size records; a set's coverage (mh_a2c_link_stats) is the summed
+ * count of every row that counts for it, the rows of dropped entries
+ * included.  A codon beyond the group's extent is legal: every row is blank
+ * there.  After mh_a2c_part_count the rows are this rank's share.
+ * *n_entries (may be NULL) = entries kept.  -3: n_sets < 1, a set of 0 or
+ * more than 12 codons, a frame outside 0..2, a negative codon,
+ * min_count < 1, a slot without a load, no group g. */
+int mh_a2c_link(mh_ctx *ctx, int slot, int64_t g, int n_sets, const int32_t *set_first,
+                const int32_t *frame, const int32_t *codon, int64_t min_count, int64_t *n_entries);
+/* The entries of the last mh_a2c_link in report order (sets as given, then
+ * count descending, then haplotype bytes ascending): set and count per entry,
+ * and one haplotype per line in haplotypes.  haplotypes NULL: *used = bytes
+ * needed. */
+int mh_a2c_link_entries(mh_ctx *ctx, int slot, int32_t *set, int64_t *count, char *haplotypes,
+                        size_t cap, size_t *used);
+/* Of the last mh_a2c_link: coverage[s] (may be NULL) per set; stats3 = (set,
+ * row) pairs that counted, distinct entries on the device, entries copied to
+ * the host; *ms (may be NULL) = host wall ms of the call, device work
+ * included. */
+int mh_a2c_link_stats(mh_ctx *ctx, int slot, int64_t *coverage, int64_t *stats3, double *ms);
 
 /* ---- aln2counts counting split over the ranks of a job (the same
  * aln2counts.py:115-172 loops; the counters are sums and a first row is a

@@ -45,6 +45,11 @@
 //                 pairs of a call in an open-addressing table, per distinct
 //                 key the summed count and the first row, then the occupied
 //                 slots as entries.  a2c_group_strings is its host side.
+//   k_a2c_link, k_a2c_link_compact
+//                 linked amino acids (mh_a2c_link, the section at the end of
+//                 this file): per (set of codons, row) the row's codon classes
+//                 at the set's codons as one exact key, grouped by
+//                 k_a2c_tab_count.
 // Host half (below the kernels): aligned.csv as csv.DictReader reads it,
 // consecutive (refname, qcut) groups (itertools.groupby, :884-887), the
 // codon extent of every frame, the bin lists.
@@ -149,6 +154,13 @@ struct A2CState {
     std::string var_text;                     // their clipped sequences, back to back
     int64_t var_stats[4] = {0, 0, 0, 0};      // pairs kept, entries, tied at a cut, text bytes fetched
     double t_var = 0;
+    // entries of the last mh_a2c_link, in report order
+    std::vector<int32_t> link_set;            // the caller's set index of each
+    std::vector<int64_t> link_count;
+    std::string link_text;                    // one haplotype per line
+    std::vector<int64_t> link_cov;            // per set of the call
+    int64_t link_stats[3] = {0, 0, 0};        // pairs that counted, distinct entries, entries fetched
+    double t_link = 0;
     double t_parse = 0, t_count = 0, t_ins = 0;
     // a part of aligned.csv held between mh_a2c_part_open and _count (mapped)
     const char *part_text = nullptr;          // (null for an empty file)
@@ -1127,6 +1139,16 @@ void a2c_free(Ctx &c)
     c.a2c = nullptr;
 }
 
+static void a2c_clear_link(A2CState &S)
+{
+    S.link_set.clear();
+    S.link_count.clear();
+    S.link_text.clear();
+    S.link_cov.clear();
+    for (int k = 0; k < 3; ++k) S.link_stats[k] = 0;
+    S.t_link = 0;
+}
+
 static void a2c_clear_inserts(A2CState &S)
 {
     S.entries.clear();
@@ -1134,6 +1156,7 @@ static void a2c_clear_inserts(A2CState &S)
     S.var_entries.clear();
     S.var_region.clear();
     S.var_text.clear();
+    a2c_clear_link(S);
 }
 
 // The device memory of one call: every allocation is freed when the holder
@@ -2538,5 +2561,356 @@ extern "C" int mh_a2c_variant_stats(mh_ctx *ctx, int slot, int64_t *stats4, doub
     A2CState &S = *a2c_state(c, slot);
     for (int k = 0; k < 4; ++k) stats4[k] = S.var_stats[k];
     if (ms) *ms = S.t_var;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Linked amino acids: per (set of codons, row) the haplotype the row reads at
+// the set's codons, equal haplotypes of a set added up (the rule:
+// tests/linkage_oracle.py).  A codon's character is k_a2c_detail's class of
+// it: one of the 21 letters, X, '?' (partial), '-' (del); a row with a blank
+// codon in a set does not count for the set.
+//   k_a2c_link          a wavefront per row, lane = one (set, position) slot
+//                       of the pass: the row is read once for all sets.  The
+//                       key of a pair is the haplotype itself, 5 bits per
+//                       position (codes 1..24, so no key is 0) and the set's
+//                       index within the pass in bits 60..63; the lanes of a
+//                       set OR their shifted codes together with a segmented
+//                       shuffle.  A set whose first or last codon lies
+//                       outside the row's codon extent is rejected before a
+//                       byte is read.  Per-set coverage leaves as one 64-bit
+//                       atomic per set and block.
+//   k_a2c_tab_count     (shared) the keys grouped; the keys are exact, so no
+//                       verify kernel follows.
+//   k_a2c_link_compact  the occupied slots with count >= min_count as (key,
+//                       count) records; the distinct ones are counted too.
+// More sets than a pass holds (A2C_LINK_SETS sets, A2C_LINK_SLOTS lanes) go
+// in further passes.
+// ---------------------------------------------------------------------------
+namespace mh {
+
+constexpr int A2C_LINK_MAX = 12;         // codons per set: 12 x 5 bits
+constexpr int A2C_LINK_SETS = 16;        // sets per pass: 4 bits of the key
+constexpr int A2C_LINK_SLOTS = 64;       // (set, position) slots per pass: the lanes of a wave
+constexpr int A2C_LINK_BITS = 5;
+constexpr int32_t A2C_LINK_FAR = 1 << 29;   // a codon beyond every row (offset, length <= 2^28)
+// haplotype characters of the codes 1..24: the 21 letters, X, partial, del
+static const char A2C_LINK_CHARS[] = "\0ACDEFGHIKLMNPQRSTVWY*X?-";
+enum { A2C_LINK_X = 22, A2C_LINK_PARTIAL = 23, A2C_LINK_DEL = 24 };
+
+struct A2CLinkSlot {
+    int32_t codon;
+    int8_t set, pos, len, frame;     // set within the pass, position within the set, the set's codons
+};
+
+struct A2CLinkRec {
+    uint64_t key;
+    unsigned long long count;
+};
+
+struct A2CLinkArgs : A2CTable {
+    const uint8_t *text;
+    const int8_t *code;
+    const uint8_t *cls;
+    const A2CLinkSlot *slots;
+    int n_slots;
+    unsigned long long *cov;         // per set of the pass
+};
+
+__global__ __launch_bounds__(256) void k_a2c_link(A2CLinkArgs A)
+{
+    __shared__ int8_t s_code[512];
+    __shared__ uint8_t s_cls[256];
+    __shared__ unsigned long long s_cov[A2C_LINK_SETS];
+    s_code[threadIdx.x] = A.code[threadIdx.x];
+    s_code[threadIdx.x + 256] = A.code[threadIdx.x + 256];
+    s_cls[threadIdx.x] = A.cls[threadIdx.x];
+    if (threadIdx.x < A2C_LINK_SETS) s_cov[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const bool live = lane < A.n_slots;
+    A2CLinkSlot L{0, 0, 0, 1, 0};
+    if (live) L = A.slots[lane];
+    // the set's first and last codon, from the lanes that hold them
+    const int k_first = __shfl(L.codon, lane - L.pos), k_last = __shfl(L.codon, lane - L.pos + L.len - 1);
+    const int shift = A2C_LINK_BITS * L.pos;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    unsigned long long cov = 0, kept = 0;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < A.n_rows; r += n_waves) {
+        const A2CRow R = A.rows[r];
+        unsigned long long v = 0;
+        int ok = 0;
+        // codons offset // 3 .. ceil((frame + offset + len) / 3) - 1 hold bytes of the row
+        if (live && k_first >= R.off / 3 && k_last < (L.frame + R.off + R.len + 2) / 3) {
+            const int q0 = 3 * L.codon - L.frame - R.off;
+            const uint8_t *s = A.text + R.soff;
+            int c[3], inside = 0;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int q = q0 + t;
+                const bool in = q >= 0 && q < R.len;
+                c[t] = in ? s_cls[s[q]] : A2C_DASH;
+                inside += in;
+            }
+            const int a = s_code[64 * c[0] + 8 * c[1] + c[2]];
+            const int dashes = (c[0] == A2C_DASH) + (c[1] == A2C_DASH) + (c[2] == A2C_DASH);
+            const int bases = (c[0] < A2C_DASH) + (c[1] < A2C_DASH) + (c[2] < A2C_DASH);
+            int k = 0;                                   // blank
+            if (a < A2C_NAA) k = a + 1;
+            else if (dashes == 3 && inside == 3) k = A2C_LINK_DEL;
+            else if (bases == 3) k = A2C_LINK_X;
+            else if (bases) k = A2C_LINK_PARTIAL;
+            v = (unsigned long long)k << shift;
+            ok = k != 0;
+        }
+        // the lanes of a set, towards its first: codes ORed, not-blank flags ANDed
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+            const unsigned long long ov = __shfl_down(v, d);
+            const int ook = __shfl_down(ok, d);
+            if (L.pos + d < L.len) {
+                v |= ov;
+                ok &= ook;
+            }
+        }
+        if (live && L.pos == 0) {
+            A.h[(int64_t)L.set * A.n_rows + r] = ok ? (v | ((unsigned long long)L.set << 60)) : 0ull;
+            if (ok) {
+                cov += R.cnt;
+                ++kept;
+            }
+        }
+    }
+    if (cov) atomicAdd(&s_cov[L.set], cov);
+    kept = a2c_wave_sum(kept);
+    if (lane == 0 && kept) atomicAdd(&A.ctr[0], kept);
+    __syncthreads();
+    if (threadIdx.x < A2C_LINK_SETS && s_cov[threadIdx.x]) atomicAdd(&A.cov[threadIdx.x], s_cov[threadIdx.x]);
+}
+
+// The occupied slots: ctr[1] counts them, those with count >= min_count
+// leave as records (ctr[2]); one counter atomic each per wave.
+__global__ __launch_bounds__(256) void k_a2c_link_compact(A2CTable T, unsigned long long min_count,
+                                                          A2CLinkRec *out)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool used = s <= T.mask && T.tkey[s] != 0;
+    const bool keep = used && T.tcnt[s] >= min_count;
+    const unsigned long long bu = __ballot(used), bk = __ballot(keep);
+    if (!bu) return;
+    unsigned long long base = 0;
+    const int leader = __ffsll((long long)bu) - 1;
+    if (lane == leader) {
+        atomicAdd(&T.ctr[1], (unsigned long long)__popcll(bu));
+        if (bk) base = atomicAdd(&T.ctr[2], (unsigned long long)__popcll(bk));
+    }
+    base = __shfl(base, leader);
+    if (keep) out[base + __popcll(bk & ((1ull << lane) - 1))] = A2CLinkRec{T.tkey[s], T.tcnt[s]};
+}
+
+struct A2CLinkEntry {
+    int32_t set;
+    int64_t count;
+    char hap[A2C_LINK_MAX];
+    int len;
+};
+
+// One pass of mh_a2c_link: the sets [s0, s1) of the call over the nr > 0 rows
+// of group g; entries and coverage appended to ent / S.link_cov.
+static int a2c_link_pass(Ctx &c, A2CState &S, int64_t g, int s0, int s1, const int32_t *set_first,
+                         const int32_t *frame, const int32_t *codon, int64_t min_count,
+                         std::vector<A2CLinkEntry> &ent)
+{
+    const int ns = s1 - s0;
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g], np = nr * ns;
+    hipStream_t s = c.stream;
+    A2CDevMem mem;
+    A2CLinkArgs a{};
+    A2CLinkSlot *d_slots;
+    A2CLinkRec *d_rec;
+    unsigned long long ctr[3] = {0, 0, 0};
+    std::vector<A2CLinkSlot> slots;
+    for (int k = s0; k < s1; ++k)
+        for (int i = set_first[k]; i < set_first[k + 1]; ++i)
+            slots.push_back({std::min(codon[i], A2C_LINK_FAR), (int8_t)(k - s0), (int8_t)(i - set_first[k]),
+                             (int8_t)(set_first[k + 1] - set_first[k]), (int8_t)frame[k]});
+    hipError_t e = mem.alloc(d_slots, slots.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_slots, slots.data(), sizeof(A2CLinkSlot) * slots.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = mem.alloc(a.h, (size_t)np);
+    if (e == hipSuccess) e = mem.alloc(a.ctr, 3);
+    if (e == hipSuccess) e = mem.alloc(a.cov, A2C_LINK_SETS);
+    if (e == hipSuccess) e = hipMemsetAsync(a.ctr, 0, sizeof(ctr), s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.cov, 0, sizeof(unsigned long long) * A2C_LINK_SETS, s);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_link alloc");
+    a.text = S.d_text;
+    a.rows = S.d_rows + S.g_first[g];
+    a.code = S.d_code;
+    a.cls = S.d_cls;
+    a.slots = d_slots;
+    a.n_slots = (int)slots.size();
+    a.n_rows = nr;
+    a.n_pairs = np;
+    {
+        const int p0 = prof_begin(c, "k_a2c_link");
+        hipLaunchKernelGGL(k_a2c_link, dim3((unsigned)std::min<int64_t>((nr + 3) / 4, 8192)), dim3(256), 0, s, a);
+        prof_end(c, p0);
+    }
+    unsigned long long cov[A2C_LINK_SETS];
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cov, a.cov, sizeof(cov), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "k_a2c_link");
+    for (int k = 0; k < ns; ++k) S.link_cov[(size_t)(s0 + k)] = (int64_t)cov[k];
+    S.link_stats[0] += (int64_t)ctr[0];
+    if (ctr[0] == 0) return 0;
+    // ---- the table: twice the keyed pairs, as a2c_group_strings sizes it ----
+    uint64_t tsize = 1024;
+    while (tsize < 2 * ctr[0]) tsize <<= 1;
+    e = mem.alloc(a.tkey, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tcnt, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tfirst, tsize);
+    if (e == hipSuccess) e = mem.alloc(a.tclass, tsize);
+    if (e == hipSuccess) e = mem.alloc(d_rec, std::min<uint64_t>(ctr[0], tsize));
+    if (e == hipSuccess) e = hipMemsetAsync(a.tkey, 0, sizeof(uint64_t) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.tcnt, 0, sizeof(unsigned long long) * tsize, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.tfirst, 0xff, sizeof(uint32_t) * tsize, s);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_link table");
+    a.mask = tsize - 1;
+    {
+        const int p0 = prof_begin(c, "k_a2c_link_count");
+        hipLaunchKernelGGL(k_a2c_tab_count, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const A2CTable &>(a));
+        prof_end(c, p0);
+        const int p1 = prof_begin(c, "k_a2c_link_compact");
+        hipLaunchKernelGGL(k_a2c_link_compact, dim3((unsigned)((tsize + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const A2CTable &>(a), (unsigned long long)min_count, d_rec);
+        prof_end(c, p1);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "k_a2c_link_count");
+    S.link_stats[1] += (int64_t)ctr[1];
+    S.link_stats[2] += (int64_t)ctr[2];
+    std::vector<A2CLinkRec> rec(ctr[2]);
+    e = copy_sync(c, rec.data(), d_rec, sizeof(A2CLinkRec) * rec.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "mh_a2c_link fetch");
+    for (const A2CLinkRec &r : rec) {
+        A2CLinkEntry x{};
+        const int k = (int)(r.key >> 60);
+        if (k >= ns) { set_error("mh_a2c_link: the table is inconsistent"); return -3; }
+        x.set = s0 + k;
+        x.count = (int64_t)r.count;
+        x.len = set_first[x.set + 1] - set_first[x.set];
+        for (int i = 0; i < x.len; ++i) {
+            const int code = (int)((r.key >> (A2C_LINK_BITS * i)) & 31);
+            if (code < 1 || code > A2C_LINK_DEL) { set_error("mh_a2c_link: the table is inconsistent"); return -3; }
+            x.hap[i] = A2C_LINK_CHARS[code];
+        }
+        ent.push_back(x);
+    }
+    return 0;
+}
+
+}  // namespace mh
+
+extern "C" int mh_a2c_link(mh_ctx *ctx, int slot, int64_t g, int n_sets, const int32_t *set_first,
+                           const int32_t *frame, const int32_t *codon, int64_t min_count,
+                           int64_t *n_entries)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || n_sets < 1 || !set_first || !frame || !codon ||
+        min_count < 1)
+        return -3;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    A2CState &S = *a2c_state(c, slot);
+    a2c_clear_link(S);
+    if (n_entries) *n_entries = 0;
+    if (!S.counted) { set_error("mh_a2c_link: nothing is loaded in slot %d", slot); return -3; }
+    const int64_t ng = (int64_t)S.g_first.size() - 1;
+    if (g < 0 || g >= ng) { set_error("mh_a2c_link: no group %lld", (long long)g); return -3; }
+    if (set_first[0] != 0) { set_error("mh_a2c_link: set_first must start at 0"); return -3; }
+    for (int k = 0; k < n_sets; ++k) {
+        const int64_t n = (int64_t)set_first[k + 1] - set_first[k];
+        if (n < 1 || n > A2C_LINK_MAX) {
+            set_error("mh_a2c_link: set %d has %lld codons (1 .. %d)", k, (long long)n, A2C_LINK_MAX);
+            return -3;
+        }
+        if (frame[k] < 0 || frame[k] > 2) { set_error("mh_a2c_link: set %d: frame %d", k, frame[k]); return -3; }
+        for (int i = set_first[k]; i < set_first[k + 1]; ++i)
+            if (codon[i] < 0) { set_error("mh_a2c_link: set %d: negative codon", k); return -3; }
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g];
+    int rc = 0;
+    try {
+        S.link_cov.assign((size_t)n_sets, 0);
+        std::vector<A2CLinkEntry> ent;
+        // a pass: at most A2C_LINK_SETS sets, A2C_LINK_SLOTS codons, 2^32 - 1 (set, row) pairs
+        const int most = (int)std::max<int64_t>(1, std::min<int64_t>(A2C_LINK_SETS, nr ? 0xffffffffll / nr : A2C_LINK_SETS));
+        for (int s0 = 0; nr && s0 < n_sets && !rc;) {
+            int s1 = s0;
+            while (s1 < n_sets && s1 - s0 < most && set_first[s1 + 1] - set_first[s0] <= A2C_LINK_SLOTS) ++s1;
+            rc = a2c_link_pass(c, S, g, s0, s1, set_first, frame, codon, min_count, ent);
+            s0 = s1;
+        }
+        if (!rc) {
+            // report order: sets as given, count descending, haplotype bytes ascending
+            std::sort(ent.begin(), ent.end(), [](const A2CLinkEntry &x, const A2CLinkEntry &y) {
+                if (x.set != y.set) return x.set < y.set;
+                if (x.count != y.count) return x.count > y.count;
+                return memcmp(x.hap, y.hap, A2C_LINK_MAX) < 0;
+            });
+            for (const A2CLinkEntry &x : ent) {
+                S.link_set.push_back(x.set);
+                S.link_count.push_back(x.count);
+                S.link_text.append(x.hap, (size_t)x.len);
+                S.link_text.push_back('\n');
+            }
+        }
+    } catch (const std::exception &ex) {
+        set_error("mh_a2c_link: out of memory (%s)", ex.what());
+        rc = -2;
+    }
+    prof_flush(c);
+    S.t_link = ms_since(t0);
+    if (rc) {
+        const double t = S.t_link;
+        a2c_clear_link(S);
+        S.t_link = t;
+    } else if (n_entries) {
+        *n_entries = (int64_t)S.link_set.size();
+    }
+    return rc;
+}
+
+extern "C" int mh_a2c_link_entries(mh_ctx *ctx, int slot, int32_t *set, int64_t *count,
+                                   char *haplotypes, size_t cap, size_t *used)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    for (size_t k = 0; k < S.link_set.size(); ++k) {
+        if (set) set[k] = S.link_set[k];
+        if (count) count[k] = S.link_count[k];
+    }
+    if (used) *used = S.link_text.size();
+    if (haplotypes) {
+        if (cap < S.link_text.size()) { set_error("mh_a2c_link_entries: buffer too small"); return -2; }
+        memcpy(haplotypes, S.link_text.data(), S.link_text.size());
+    }
+    return 0;
+}
+
+extern "C" int mh_a2c_link_stats(mh_ctx *ctx, int slot, int64_t *coverage, int64_t *stats3, double *ms)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || !stats3) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    if (coverage) for (size_t k = 0; k < S.link_cov.size(); ++k) coverage[k] = S.link_cov[k];
+    for (int k = 0; k < 3; ++k) stats3[k] = S.link_stats[k];
+    if (ms) *ms = S.t_link;
     return 0;
 }

@@ -225,6 +225,11 @@ def _declare(L):
         'mh_a2c_variant_entries': ([_P, ctypes.c_int, _P, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
                                     ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_a2c_variant_stats': ([_P, ctypes.c_int, _P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'mh_a2c_link': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _P, _P, _P, ctypes.c_int64, _I64P],
+                        ctypes.c_int),
+        'mh_a2c_link_entries': ([_P, ctypes.c_int, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
+                                 ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_a2c_link_stats': ([_P, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         'mh_fastq_open_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 ctypes.POINTER(_P), _I64P], ctypes.c_int),
         'mh_fastq_scan_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I64P],
@@ -1097,6 +1102,43 @@ class Context:
         stats = dict(zip(self.VARIANT_STATS, (int(x) for x in st)))
         stats['ms'] = ms.value
         return out, stats
+
+    LINK_STATS = ('pairs', 'entries', 'fetched')
+
+    def a2c_link(self, slot, g, sets, min_count=1):
+        """mh_a2c_link over group g for sets = [(frame, [consensus codons])],
+        then the entries: ([(set index, count, haplotype bytes)] in report
+        order -- sets as given, count descending, haplotype ascending --,
+        stats dict of LINK_STATS plus 'coverage' (a list, one per set) and
+        'ms').  Only entries with count >= min_count come to the host;
+        coverage counts the rows of the others too."""
+        sets = [(int(f), [int(k) for k in codons]) for f, codons in sets]
+        first = np.zeros(len(sets) + 1, dtype=np.int32)
+        if sets:
+            np.cumsum([len(codons) for _, codons in sets], out=first[1:])
+        frames = np.array([f for f, _ in sets] or [0], dtype=np.int32)
+        flat = np.array([k for _, codons in sets for k in codons] or [0], dtype=np.int32)
+        n = ctypes.c_int64()
+        check(lib().mh_a2c_link(self.h, slot, g, len(sets), _ptr(first), _ptr(frames), _ptr(flat),
+                                int(min_count), ctypes.byref(n)), 'mh_a2c_link')
+        k = n.value
+        which = np.zeros(max(k, 1), np.int32)
+        cnt = np.zeros(max(k, 1), np.int64)
+        used = ctypes.c_size_t()
+        check(lib().mh_a2c_link_entries(self.h, slot, _ptr(which), _ptr(cnt), None, 0, ctypes.byref(used)),
+              'mh_a2c_link_entries')
+        buf = ctypes.create_string_buffer(max(used.value, 1))
+        check(lib().mh_a2c_link_entries(self.h, slot, None, None, buf, len(buf), ctypes.byref(used)),
+              'mh_a2c_link_entries')
+        haps = buf.raw[:used.value].split(b'\n')[:k]
+        cov = np.zeros(max(len(sets), 1), dtype=np.int64)
+        st = np.zeros(3, dtype=np.int64)
+        ms = ctypes.c_double()
+        check(lib().mh_a2c_link_stats(self.h, slot, _ptr(cov), _ptr(st), ctypes.byref(ms)), 'mh_a2c_link_stats')
+        stats = dict(zip(self.LINK_STATS, (int(x) for x in st)))
+        stats['coverage'] = [int(x) for x in cov[:len(sets)]]
+        stats['ms'] = ms.value
+        return [(int(which[i]), int(cnt[i]), haps[i]) for i in range(k)], stats
 
     def a2c_timing(self, slot):
         out = np.zeros(3, dtype=np.float64)

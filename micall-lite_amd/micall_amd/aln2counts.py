@@ -38,6 +38,10 @@ unchanged.  Differences that never reach an output file:
     (aln2counts.py:595-603) are counted, as X, partial and del, only when
     asked for (SequenceReport.write_amino_detail, aln2counts(amino_detail_csv=),
     --amino_detail_csv): k_a2c_detail through mh_a2c_codon_detail;
+  * the amino acids single reads link at chosen positions of a coordinate
+    region, a report the reference does not have, are counted only when asked
+    for (SequenceReport.count_linkage / write_linkage, aln2counts(linkage_csv=,
+    linkage_positions=), --linkage_csv): k_a2c_link through mh_a2c_link;
   * an InsertionWriter fed by a SequenceReport reads the run's rows from the
     device, so its nuc_seqs stays empty;
   * characters other than A C G T N - n, negative offsets and counts of 2**32
@@ -87,7 +91,9 @@ _SCHEMA = {
     'failed': ['seed', 'region', 'qcut', 'queryseq', 'refseq'],
     'insert': ['seed', 'region', 'qcut', 'left', 'insert', 'count', 'before'],
     'coverage': ['avg_coverage', 'coverage_region', 'region_width'],
+    'linkage': ['seed', 'region', 'q-cutoff', 'positions', 'haplotype', 'count', 'coverage'],
 }
+LINKAGE_MAX_POSITIONS = 12            # positions of one linked set (mh_a2c_link: 5 key bits each)
 
 SLOT_REPORT, SLOT_INSERTS = 0, 1      # device row tables (mh_a2c slots) used here
 _CODON_CHARS = codon_chars()
@@ -333,6 +339,73 @@ class _CoordinateMap(object):
         return len(self.conseq_index)
 
 
+def _check_linkage(positions, min_count=1):
+    """The linked sets a caller gave, {region name: [set, ...]}, as lists of
+    ints; ValueError naming the region and the set for one that is empty,
+    longer than LINKAGE_MAX_POSITIONS, not strictly increasing or not made of
+    integers >= 1, and for min_count < 1.  No device is touched."""
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError('linkage: min_count must be an integer >= 1, not %r' % (min_count,))
+    if not isinstance(positions, dict):
+        raise ValueError('linkage: positions must map region names to lists of sets')
+    checked = {}
+    for region, sets in positions.items():
+        if not isinstance(region, str) or not isinstance(sets, (list, tuple)):
+            raise ValueError('linkage: region %r must be a name with a list of sets' % (region,))
+        checked[region] = []
+        for s, chosen in enumerate(sets):
+            where = 'linkage: region %s, set %d %r' % (region, s, chosen)
+            if not isinstance(chosen, (list, tuple)) or not chosen:
+                raise ValueError(where + ' is empty or not a list')
+            if len(chosen) > LINKAGE_MAX_POSITIONS:
+                raise ValueError(where + ' holds more than %d positions' % LINKAGE_MAX_POSITIONS)
+            if any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) or p < 1 for p in chosen):
+                raise ValueError(where + ' must hold integers >= 1')
+            if any(b <= a for a, b in zip(chosen, chosen[1:])):
+                raise ValueError(where + ' is not strictly increasing')
+            checked[region].append([int(p) for p in chosen])
+    return checked
+
+
+def _load_linkage(positions):
+    """linkage_positions of aln2counts(): the mapping itself, or the path of
+    a JSON file that holds only that mapping."""
+    if isinstance(positions, (str, bytes, os.PathLike)):
+        with open(positions) as f:
+            positions = jsonlib.load(f)
+    return positions
+
+
+def _merge_linkage(parts):
+    """Every rank's a2c_link results of one call, [(entries, coverage)], added
+    up by (set, haplotype): the keys are exact, so equal haplotypes of a set
+    are one entry whichever rank counted them.  Report order."""
+    total, coverage = {}, None
+    for found, cov in parts:
+        coverage = list(cov) if coverage is None else [a + b for a, b in zip(coverage, cov)]
+        for s, n, hap in found:
+            total[s, hap] = total.get((s, hap), 0) + n
+    return sorted(((s, n, hap) for (s, hap), n in total.items()), key=lambda e: (e[0], -e[1], e[2])), coverage
+
+
+_LINK_RECORD = np.dtype([('set', '<i4'), ('count', '<i8'), ('hap', 'S%d' % LINKAGE_MAX_POSITIONS)])
+
+
+def _pack_linkage(found, coverage):
+    """A rank's a2c_link result on the wire: the per-set coverage, then
+    fixed-size (set, count, haplotype) records."""
+    rec = np.zeros(len(found), dtype=_LINK_RECORD)
+    for k, (s, n, hap) in enumerate(found):
+        rec[k] = (s, n, hap)
+    return np.asarray(coverage, dtype='<i8').tobytes() + rec.tobytes()
+
+
+def _unpack_linkage(blob, n_sets):
+    coverage = np.frombuffer(blob[:8 * n_sets], dtype='<i8')
+    rec = np.frombuffer(blob[8 * n_sets:], dtype=_LINK_RECORD)
+    return [(int(r['set']), int(r['count']), bytes(r['hap'])) for r in rec], [int(c) for c in coverage]
+
+
 # ---------------------------------------------------------------------------
 # SequenceReport
 # ---------------------------------------------------------------------------
@@ -397,6 +470,8 @@ class SequenceReport(object):
         self._variants_counted = False
         self.variant_stats = None
         self._job_detail = None
+        self.linkage_unplaced = []
+        self.linkage_stats = None
         if run is not None:
             self.seed, self.qcut = run.seed, run.qcut
             self.insert_writer.start_group(run.seed, run.qcut)
@@ -701,6 +776,81 @@ class SequenceReport(object):
         out.writerows(dict(seed=self.seed, qcut=self.qcut, region=name, index=i, count=count, seq=seq)
                       for name in sorted(variants) for i, (count, seq) in enumerate(variants[name]))
 
+    def write_linkage_header(self, linkage_file):
+        _csv_writer(linkage_file, 'linkage').writeheader()
+
+    def count_linkage(self, positions, min_count=1):
+        """The amino acids the reads of the run just read link at chosen
+        positions (not in the reference).  positions: {coordinate region:
+        [set, ...]}, a set being 1 to 12 strictly increasing 1-based
+        amino-acid positions of the region.  Returns [(region, set index,
+        the set, [(haplotype, count), ...], coverage)] for every set placed in
+        this run, regions in name order, sets as given.
+
+        A set is placed when every position has a consensus codon in the
+        region's map; the others are listed in linkage_unplaced as (region,
+        set index).  A region that is not one of the seed's, or that no
+        reading frame aligned to, is passed over.  A row's character at a
+        position is the class amino_detail.csv counts its codon in -- the
+        letter, X, '?' for partial, '-' for del -- and a row with a blank
+        codon (padding only, or only the gap between the mates) at any
+        position of a set does not count for the set.  Equal haplotypes add
+        their counts up; the list holds those with count >= min_count, by
+        count descending then haplotype ascending; coverage counts every row
+        that counts, the dropped haplotypes' too.  One device call for all
+        sets of the run (mh_a2c_link; its figures in linkage_stats), made
+        only when asked.  In a sharded job every rank counts its own rows and
+        the entries are added up by (set, haplotype)."""
+        positions = _check_linkage(positions, min_count)
+        self.linkage_unplaced = []
+        self.linkage_stats = None
+        refs = getattr(self, 'coordinate_refs', {})
+        for name in sorted(positions):
+            if name in refs:
+                for s, chosen in enumerate(positions[name]):
+                    if chosen[-1] > len(refs[name]):
+                        raise ValueError('linkage: region %s, set %d %r reaches past the %d positions of '
+                                         'the coordinate reference' % (name, s, chosen, len(refs[name])))
+        asked, sets = [], []
+        for name in sorted(positions):
+            cmap = getattr(self, '_coord_maps', {}).get(name) if name in refs else None
+            if cmap is None or not len(cmap):
+                continue
+            codon_of = dict(zip(cmap.positions.tolist(), cmap.conseq_index.tolist()))
+            for s, chosen in enumerate(positions[name]):
+                codons = [codon_of.get(p, -1) for p in chosen]
+                if min(codons) < 0:
+                    self.linkage_unplaced.append((name, s))
+                else:
+                    asked.append((name, s, chosen))
+                    sets.append((cmap.frame, codons))
+        run = getattr(self, '_run', None)
+        if not sets or run is None:
+            return []
+        if _SHARD is not None and run.slot == SLOT_REPORT:
+            from .sharded_io import _checked
+            mine, self.linkage_stats = _checked(_SHARD, lambda: run.ctx.a2c_link(run.slot, run.group, sets, 1))
+            found, coverage = _merge_linkage(
+                _unpack_linkage(blob, len(sets))
+                for blob in _SHARD.all_gather_bytes(_pack_linkage(mine, self.linkage_stats['coverage'])))
+            found = [e for e in found if e[1] >= min_count]
+        else:
+            found, self.linkage_stats = run.ctx.a2c_link(run.slot, run.group, sets, min_count)
+            coverage = self.linkage_stats['coverage']
+        out = [(name, s, chosen, [], coverage[k]) for k, (name, s, chosen) in enumerate(asked)]
+        for k, count, hap in found:
+            out[k][3].append((hap.decode('ascii'), count))
+        return out
+
+    def write_linkage(self, linkage_file, positions, min_count=1):
+        """linkage.csv's rows of this run: per placed set (count_linkage) one
+        row per haplotype, with the set's positions joined by ';' and its
+        coverage."""
+        out = csv.writer(linkage_file, lineterminator=os.linesep)
+        for name, _s, chosen, found, coverage in self.count_linkage(positions, min_count):
+            where = ';'.join(str(p) for p in chosen)
+            out.writerows([self.seed, name, self.qcut, where, hap, count, coverage] for hap, count in found)
+
     def write_failure(self, fail_file):
         """One row per coordinate region that no reading frame aligned to."""
         out = _csv_writer(fail_file, 'failed')
@@ -898,7 +1048,8 @@ _SHARD = None      # the job's Shard while a sharded aln2counts runs (InsertionW
 def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
                coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
-               nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None):
+               nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None, linkage_csv=None,
+               linkage_positions=None, linkage_min_count=1):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -915,6 +1066,13 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     at the position that amino.csv leaves out, counted on the device only
     when this is asked for; its ins and clip columns come from the same two
     inputs (read once for both detail files) and stay empty without them.
+    linkage_csv takes the amino acids single reads link at the positions of
+    linkage_positions (SequenceReport.count_linkage): {coordinate region:
+    [set of 1-based positions, ...]}, or the path of a JSON file holding only
+    that mapping; haplotypes counted fewer than linkage_min_count times are
+    left out (their rows still count in coverage).  A bad set raises
+    ValueError before any device work; linkage_positions without linkage_csv
+    does nothing.
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -926,13 +1084,21 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     does when any rank was given variants_csv (the variants are counted over
     all rows of a run at once, not merged across ranks).  When any rank was
     given amino_detail_csv every rank counts the codon classes of its own rows
-    and the tables are added up."""
+    and the tables are added up.  When any rank was given linkage_csv every
+    rank counts rank 0's sets over its own rows and the entries are added up
+    by (set, haplotype); with variants_csv as well the whole call is
+    unsplit."""
     global _SHARD
+    link = None                 # (sets, min_count) when linkage.csv is asked for
+    if linkage_csv is not None:
+        if linkage_positions is None:
+            raise ValueError('linkage: linkage_csv needs linkage_positions')
+        link = _check_linkage(_load_linkage(linkage_positions), linkage_min_count), linkage_min_count
     sh = session.shard()
     SHARD_STATS.clear()
     session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
-               coverage_summary_csv, variants_csv, nuc_detail_csv, amino_detail_csv)
+               coverage_summary_csv, variants_csv, nuc_detail_csv, amino_detail_csv, linkage_csv)
     with session.writer_stage(*handles) as stage:
         split = sh is not None
         if split:
@@ -942,6 +1108,11 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                 SHARD_STATS.update(mode='unsplit', reason='variants_csv')
         # asked for on some rank: then every rank enters the sum of the tables
         job_detail = split and not _agree_ok(sh, amino_detail_csv is None)
+        job_link = None
+        if split and not _agree_ok(sh, linkage_csv is None):
+            # the sets are rank 0's, so that every rank enters the same collectives
+            spec = sh.all_gather_bytes(jsonlib.dumps(link).encode() if link else b'')[0]
+            job_link = tuple(jsonlib.loads(spec.decode())) if spec else None
         groups = _load_sharded(sh, aligned_csv) if split else None
         if groups is None:
             if stage.active:
@@ -949,7 +1120,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
                             nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv,
-                            amino_detail_csv=amino_detail_csv)
+                            amino_detail_csv=amino_detail_csv, linkage_csv=linkage_csv, link=link)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -958,7 +1129,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
             _aln2counts(aligned_csv, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5],
                         callback if stage.active else None, outs[6], json, groups=groups,
                         clipping_csv=clipping_csv, nuc_detail_csv=outs[8],
-                        conseq_ins_csv=conseq_ins_csv, amino_detail_csv=outs[9], job_detail=job_detail)
+                        conseq_ins_csv=conseq_ins_csv, amino_detail_csv=outs[9], job_detail=job_detail,
+                        linkage_csv=None if job_link is None else outs[10] or io.StringIO(), link=job_link)
         finally:
             _SHARD = None
 
@@ -1021,7 +1193,7 @@ def _load_sharded(sh, aligned_csv):
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
                 variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None,
-                amino_detail_csv=None, job_detail=False):
+                amino_detail_csv=None, job_detail=False, linkage_csv=None, link=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -1050,6 +1222,9 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if amino_detail_csv is not None:
         report.write_amino_detail_header(amino_detail_csv)
         per_run.append(lambda: report.write_amino_detail(amino_detail_csv, clipping, insertions))
+    if linkage_csv is not None:
+        report.write_linkage_header(linkage_csv)
+        per_run.append(lambda: report.write_linkage(linkage_csv, *link))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -1125,7 +1300,7 @@ def _read_conseq_ins(conseq_ins_csv):
     return insertions
 
 
-def _arguments():
+def _arguments(argv=None):
     cli = argparse.ArgumentParser(description='aln2counts on the MI355X: counts, consensus and '
                                               'insertions from aligned.csv.')
     cli.add_argument('aligned_csv', type=argparse.FileType('r'), help='aligned.csv from sam2aln')
@@ -1147,7 +1322,13 @@ def _arguments():
                      help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
     cli.add_argument('--amino_detail_csv', type=argparse.FileType('w'),
                      help='output: amino.csv with X, partial, del, ins, clip and coverage counts')
-    return cli.parse_args()
+    cli.add_argument('--linkage_csv', type=argparse.FileType('w'),
+                     help='output: amino acids linked by single reads at the positions of --linkage_positions')
+    cli.add_argument('--linkage_positions', metavar='FILE.json',
+                     help='input: {coordinate region: [[1-based amino-acid positions], ...]} as JSON')
+    cli.add_argument('--linkage_min_count', type=int, default=1, metavar='N',
+                     help='leave out linked haplotypes counted fewer than N times (default 1)')
+    return cli.parse_args(argv)
 
 
 parseArgs = _arguments
@@ -1158,7 +1339,9 @@ def main():
     aln2counts(a.aligned_csv, a.nuc_csv, a.amino_csv, a.coord_ins_csv, a.conseq_csv,
                a.failed_align_csv, a.nuc_variants_csv, variants_csv=a.variants_csv,
                clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv,
-               conseq_ins_csv=a.conseq_ins_csv, amino_detail_csv=a.amino_detail_csv)
+               conseq_ins_csv=a.conseq_ins_csv, amino_detail_csv=a.amino_detail_csv,
+               linkage_csv=a.linkage_csv, linkage_positions=a.linkage_positions,
+               linkage_min_count=a.linkage_min_count)
 
 
 if __name__ == '__main__':
