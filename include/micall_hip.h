@@ -551,6 +551,34 @@ int mh_sam2aln_clipping_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *writ
  * mh_sam2aln_part_names prints).  *n = rows; arrays NULL: only *n. */
 int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *count, int64_t cap,
                            int64_t *n);
+/* Mate concordance of the last sam2aln call on this context, over the paired
+ * units that reach the merge (the units clipping.csv counts, FLAG bit 1 set),
+ * whatever the q-cutoffs.  Each mate is expanded as apply_cigar expands it.
+ * which 0, concordance.csv (refname,pos,overlap,mismatch,indel,nocall,
+ * unresolved): per reference and 1-based position both mates align (M or D),
+ * the units (overlap), those whose two bytes differ -- nocall when either is
+ * 'N', else indel when either is '-', else mismatch -- and those that differ
+ * with qualities closer than 5 (unresolved); rows with overlap > 0, names
+ * sorted as strings, then positions.  which 1, cycle_concordance.csv
+ * (read,by,value,compared,mismatch): per read (1: FLAG 0x40, else 2) and
+ * sequencing cycle (by = cycle) or quality - 33 (by = quality) the bases
+ * compared with the mate's base -- both read bases, neither 'N' -- and found
+ * different; rows with compared > 0, by read, cycles before qualities, then
+ * value.  '\n' line ends.  Nothing is computed before the first of these three
+ * calls asks: the pass (k_s2a_conc, k_s2a_conc_scan) then runs once over the
+ * rows and units the call left on the device, so ask before the next sam2aln
+ * or mapping call.  buf NULL: only *used = bytes needed.  -3 with a message
+ * naming the reference when its paired rows span more than 2^26 positions. */
+int mh_sam2aln_concordance(mh_ctx *ctx, int which, char *buf, size_t cap, size_t *used);
+/* The same text written to fd at offset with pwrite; *written = its size. */
+int mh_sam2aln_concordance_write(mh_ctx *ctx, int which, int fd, int64_t offset, int64_t *written);
+/* The same counts as arrays in the texts' row order.  Positions: name_id (as
+ * in mh_sam2aln_clip_counts), pos and five counts per row (overlap, mismatch,
+ * indel, nocall, unresolved); *n = rows.  Reads: five int64 per row (read, by
+ * with 0 cycle and 1 quality, value, compared, mismatch); *read_n = rows.
+ * Arrays NULL: only *n and *read_n. */
+int mh_sam2aln_conc_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *counts5, int64_t cap,
+                           int64_t *n, int64_t *reads5, int64_t read_cap, int64_t *read_n);
 /* conseq_ins.csv of the last sam2aln call on this context: the insertions
  * that remap's last pass left out of the consensus, merged per unit as the
  * reference's merge_inserts merges them and counted per distinct string

@@ -75,6 +75,29 @@ struct S2AClip {
             *d_n = nullptr;                                  // d_n: pairs per reference, then the error flag
 };
 
+// mate concordance of the last call (mh_sam2aln_concordance), counted on the
+// first request from the same rows and units: per consensus position the
+// paired units whose mates both align it and how they disagree there, and per
+// (read, cycle) and (read, quality) the bases compared and found different
+enum { CONC_OVERLAP = 0, CONC_MISMATCH = 1, CONC_INDEL = 2, CONC_NOCALL = 3, CONC_UNRESOLVED = 4,
+       CONC_PLANES = 5 };
+
+struct S2AConc {
+    bool done = false;
+    std::vector<int32_t> name;          // per (reference, position) with overlap > 0, by (name as
+    std::vector<int64_t> pos;           //   Python sorts str, pos): index into S2AState::names, position
+    std::vector<int32_t> count;         // CONC_PLANES per row
+    std::vector<int64_t> reads;         // per key with compared > 0, in file order: read, by (0 cycle,
+                                        //   1 quality), value, compared, mismatch
+    std::string text[2];                // concordance.csv, cycle_concordance.csv, formatted on first use
+    bool text_valid[2] = {false, false};
+    int64_t *d_lo = nullptr, *d_base = nullptr;              // per reference: window start, offset in a plane
+    int32_t *d_wlen = nullptr, *d_acc = nullptr, *d_idx = nullptr, *d_cnt = nullptr,
+            *d_n = nullptr;                                  // d_n: rows per reference, then the error flag
+    uint8_t *d_orient = nullptr;                             // per merge unit: k_s2a_conc's orientation bits
+    unsigned long long *d_rd = nullptr;                      // the per-read sums (64-bit)
+};
+
 // merged insertions of the last call (mh_sam2aln_conseq_ins), counted on the
 // first request from the same rows and units.  One record per (listed unit,
 // consensus key); one entry per (record, q-cutoff): entry = record * n_cut + k
@@ -167,6 +190,7 @@ struct S2AState {
     double t_parse = 0, t_device = 0, t_format[3] = {0, 0, 0};
     S2AClip clip;
     S2AIns ins;
+    S2AConc conc;
     // shape of the last k_s2a_merge launch, kept for mh_test_sam2aln_info
     // (host bookkeeping; nothing reads it otherwise).  wpb and blocks stay 0
     // when the call was refused before the launch
@@ -202,6 +226,7 @@ inline void s2a_begin(Ctx &c, S2AState &S)
     S.clip.state = CLIP_NONE;
     S.clip.text_valid = false;
     S.ins.done = S.ins.text_valid = false;
+    S.conc.done = S.conc.text_valid[0] = S.conc.text_valid[1] = false;
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
     S.out_valid = 0;
 }
@@ -228,6 +253,9 @@ int s2a_clip_run(Ctx &c, S2AState &S);
 // k_s2a_ins_rec, k_s2a_ins_merge and the grouping over the units of the last
 // s2a_run that hold an I op, once per call: S.ins's rows and totals
 int s2a_ins_run(Ctx &c, S2AState &S);
+// k_s2a_conc and k_s2a_conc_scan over the paired units of the last s2a_run,
+// once per call: S.conc's position rows and read table
+int s2a_conc_run(Ctx &c, S2AState &S);
 // Units, failure causes, group names and QNAMEs of the resident rows (one
 // per read, in read order) instead of s2a_parse: S.pos, S.flag, S.n_cig,
 // S.cig_off and S.cig hold the rows as k_s2a_stage wrote them; sam_ref[r]

@@ -30,6 +30,11 @@
 //                 consensus position, merged as merge_inserts does
 //                 (sam2aln.py:240-273) and counted per distinct string
 //                 (conseq_ins.csv)
+//   k_s2a_conc, k_s2a_conc_scan   only when mh_sam2aln_concordance asks: where
+//                 the two mates of a unit both align and how often they
+//                 disagree, per consensus position and per read cycle and
+//                 quality (concordance.csv, cycle_concordance.csv; no
+//                 reference code)
 // Bit-for-bit specification: the reference itself (tests/golden/e2e/*/aligned.csv
 // etc. were produced by running micall.core.sam2aln on the same remap.csv).
 #include <fcntl.h>
@@ -85,6 +90,14 @@ static void s2a_free_device(S2AState &S)
     I.d_h = I.d_tkey = nullptr;
     I.d_out = I.d_gather = nullptr;
     I.done = false;
+    S2AConc &Q = S.conc;
+    hipFree(Q.d_lo); hipFree(Q.d_base); hipFree(Q.d_wlen); hipFree(Q.d_acc); hipFree(Q.d_idx);
+    hipFree(Q.d_cnt); hipFree(Q.d_n); hipFree(Q.d_orient); hipFree(Q.d_rd);
+    Q.d_lo = Q.d_base = nullptr;
+    Q.d_wlen = Q.d_acc = Q.d_idx = Q.d_cnt = Q.d_n = nullptr;
+    Q.d_orient = nullptr;
+    Q.d_rd = nullptr;
+    Q.done = false;
     S.dcap.clear();
 }
 
@@ -1166,6 +1179,480 @@ static int s2a_clip_of(mh_ctx *ctx, const char *what, bool text, S2AState **out)
 }
 
 // ---------------------------------------------------------------------------
+// Mate concordance (concordance.csv, cycle_concordance.csv; DESIGN.md section
+// 6, "Mate concordance").  A paired unit that reaches the merge is expanded as
+// apply_cigar expands it; at every position y both mates map (M or D) it adds
+// 1 to overlap and, when the mates' bytes differ, 1 to one of mismatch, indel,
+// nocall, and 1 to unresolved when their qualities are closer than 5.  Where
+// both mates hold a read base other than 'N', each adds 1 to compared (and to
+// mismatch when the bytes differ) at its (read, cycle) and (read, quality).
+//
+// k_s2a_conc       one wave per unit: the op offsets of both mates by the
+//                  merge's lane-parallel scan (in LDS), then the intersection
+//                  of the two mapped intervals 64 positions at a time, each
+//                  lane looking both mates' bytes up in seq / qual.  overlap is
+//                  two steps into the reference's difference array (plane 0);
+//                  the four sparse classes are planes 1..4 of the same array.
+//                  Steps and classes go through the block's LDS table (keyed
+//                  by plane and index, CONC_SLOTS slots, CONC_PROBES probes,
+//                  then straight to HBM) and are flushed with one atomic per
+//                  used slot.  The per-read table is dense in LDS (32-bit)
+//                  while a read's slots fit in CONC_READ_LDS, and flushed once
+//                  per block with 64-bit adds; a longer read's adds go
+//                  straight to the 64-bit table in HBM.  Integer adds only.
+// k_s2a_conc_scan  one block per reference: the running sum of plane 0 as
+//                  k_s2a_clip_scan runs it, and the positions with overlap > 0
+//                  compacted in position order with their five counts.
+// ---------------------------------------------------------------------------
+constexpr int CONC_SLOTS = 1024;      // LDS table of k_s2a_conc (12 KiB a block)
+constexpr int CONC_PROBES = 8;
+constexpr int CONC_WPB = 4;
+constexpr int CONC_READ_LDS = 2048;   // slots (cycles + 256 qualities) of one read kept in LDS at most
+constexpr int CONC_UNITS_PER_WAVE = 16;  // a block's flush is one atomic per used slot: shared by 64 units
+constexpr int64_t CONC_BLOCK_CAP = 1024;
+
+struct ConcArgs {
+    const uint8_t *seq, *qual;
+    const int64_t *soff;
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int64_t *units;     // per merge unit: row1, row2 (-1: single)
+    const int32_t *uref;
+    const uint8_t *orient;    // per merge unit: bit 0 row1 is read 2, bit 1 row1 is reversed; bits 2, 3 row2
+    int64_t n;
+    const int64_t *lo, *base; // per reference: first position of its window, its offset in a plane
+    const int32_t *wlen;      // per reference: positions in its window (a plane holds wlen + 1)
+    int64_t total;            // entries of one plane
+    int32_t *acc;             // CONC_PLANES planes
+    unsigned long long *rd;   // [compared, mismatch][read][stride]: slot = cycle, or max_len + 1 + quality byte
+    int stride, max_len, rd_lds, ops_cap;
+    int32_t *err;             // set when a position or a cycle falls outside its table
+};
+
+__device__ __forceinline__ void conc_add(const ConcArgs &A, unsigned long long *tkey, int32_t *tval,
+                                         int plane, int64_t g, int d)
+{
+    const int64_t at = (int64_t)plane * A.total + g;
+    const unsigned long long key = (unsigned long long)at + 1ull;
+    unsigned s = (unsigned)hash_key(key) & (CONC_SLOTS - 1);
+    for (int t = 0; t < CONC_PROBES; ++t, s = (s + 1) & (CONC_SLOTS - 1)) {
+        const unsigned long long old = atomicCAS(&tkey[s], 0ull, key);
+        if (old == 0ull || old == key) {
+            atomicAdd(&tval[s], d);
+            return;
+        }
+    }
+    atomicAdd(&A.acc[at], d);
+}
+
+__device__ __forceinline__ void conc_read_add(const ConcArgs &A, uint32_t *rl, int read, int slot,
+                                              bool differ)
+{
+    const int i = read * A.stride + slot;
+    if (A.rd_lds) {
+        atomicAdd(&rl[i], 1u);
+        if (differ) atomicAdd(&rl[2 * A.stride + i], 1u);
+    } else {
+        atomicAdd(&A.rd[i], 1ull);
+        if (differ) atomicAdd(&A.rd[2 * A.stride + i], 1ull);
+    }
+}
+
+// the op offsets of row r as k_s2a_merge scans them: oref[o], ord[o] = the
+// reference and read offset op o starts at (ord -1: a D op), one past the
+// last op the totals.  Returns the reference span; read_len = the read bases
+__device__ __forceinline__ int conc_ops(const ConcArgs &A, int64_t r, int32_t *oref, int32_t *ord,
+                                        int lane, int &read_len)
+{
+    const int nc = A.n_cig[r];
+    const uint32_t *ops = A.cig + A.cig_off[r];
+    int rf0 = 0, rd0 = 0;
+    for (int o0 = 0; o0 < nc; o0 += 64) {
+        const int o = o0 + lane;
+        int dref = 0, dread = 0, isd = 0;
+        if (o < nc) {
+            const uint32_t op = ops[o];
+            const int n = (int)(op >> 4), t = (int)(op & 15);
+            if (t == MH_OP_M) { dref = n; dread = n; }
+            else if (t == MH_OP_D) { dref = n; isd = 1; }
+            else dread = n;                      // I, S (checked on the host)
+        }
+        const int iref = s2a_scan(dref, lane), iread = s2a_scan(dread, lane);
+        if (o < nc) {
+            oref[o] = rf0 + iref - dref;
+            ord[o] = isd ? -1 : rd0 + iread - dread;
+        }
+        rf0 += __shfl(iref, 63, 64);
+        rd0 += __shfl(iread, 63, 64);
+    }
+    if (lane == 0) { oref[nc] = rf0; ord[nc] = rd0; }
+    read_len = rd0;
+    return rf0;
+}
+
+// the mate's byte, quality and read index (-1: deleted) at offset t of its span
+__device__ __forceinline__ void conc_at(const int32_t *oref, const int32_t *ord, const uint8_t *s,
+                                        const uint8_t *q, int t, int read_len, unsigned char &c,
+                                        unsigned char &qq, int &x)
+{
+    int o = 0;
+    while (oref[o + 1] <= t) ++o;
+    const int rd = ord[o];
+    c = '-'; qq = ' '; x = -1;
+    if (rd >= 0) {
+        const int i = rd + (t - oref[o]);
+        if (i < read_len) { x = i; c = s[i]; qq = q[i]; }
+    }
+}
+
+__global__ __launch_bounds__(64 * CONC_WPB) void k_s2a_conc(ConcArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ unsigned long long tkey[CONC_SLOTS];
+    __shared__ int32_t tval[CONC_SLOTS];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wpb = blockDim.x >> 6;
+    const int nrl = A.rd_lds ? 4 * A.stride : 0;
+    uint32_t *rl = (uint32_t *)smem;
+    int32_t *wops = (int32_t *)(smem + (((size_t)nrl * 4 + 15) & ~(size_t)15)) +
+                    (size_t)wv * 4 * (A.ops_cap + 1);
+    // named, not indexed by a run-time mate: nothing here lives in scratch memory
+    int32_t *oref0 = wops, *ord0 = wops + (A.ops_cap + 1);
+    int32_t *oref1 = wops + 2 * (A.ops_cap + 1), *ord1 = wops + 3 * (A.ops_cap + 1);
+    for (int s = threadIdx.x; s < CONC_SLOTS; s += blockDim.x) { tkey[s] = 0ull; tval[s] = 0; }
+    for (int s = threadIdx.x; s < nrl; s += blockDim.x) rl[s] = 0u;
+    __syncthreads();
+
+    for (int64_t u = (int64_t)blockIdx.x * wpb + wv; u < A.n; u += (int64_t)gridDim.x * wpb) {
+        const int64_t r0 = A.units[2 * u], r1 = A.units[2 * u + 1];
+        if (r1 < 0) continue;                         // an unpaired unit: nothing to compare
+        int len0, len1;
+        const int rf0 = conc_ops(A, r0, oref0, ord0, lane, len0);
+        const int rf1 = conc_ops(A, r1, oref1, ord1, lane, len1);
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const int64_t p0 = A.pos[r0], p1 = A.pos[r1];
+        const int64_t lo = p0 > p1 ? p0 : p1;
+        const int64_t hi = p0 + rf0 < p1 + rf1 ? p0 + rf0 : p1 + rf1;
+        if (hi > lo) {
+            const int ref = A.uref[u];
+            const int64_t w0 = A.lo[ref], gb = A.base[ref];
+            if (lo < w0 || hi - w0 > (int64_t)A.wlen[ref]) {   // the host sized the window from the same rows
+                if (lane == 0) atomicExch(A.err, 1);
+            } else {
+                if (lane == 0) {
+                    conc_add(A, tkey, tval, CONC_OVERLAP, gb + (lo - w0), 1);
+                    conc_add(A, tkey, tval, CONC_OVERLAP, gb + (hi - w0), -1);
+                }
+                const int ob = A.orient[u];
+                const int read0 = ob & 1, rev0 = (ob >> 1) & 1, read1 = (ob >> 2) & 1, rev1 = (ob >> 3) & 1;
+                const uint8_t *s0 = A.seq + A.soff[r0], *q0 = A.qual + A.soff[r0];
+                const uint8_t *s1 = A.seq + A.soff[r1], *q1 = A.qual + A.soff[r1];
+                for (int64_t y0 = lo; y0 < hi; y0 += 64) {
+                    const int64_t y = y0 + lane;
+                    if (y >= hi) continue;
+                    unsigned char c0, c1, b0, b1;
+                    int x0, x1;
+                    conc_at(oref0, ord0, s0, q0, (int)(y - p0), len0, c0, b0, x0);
+                    conc_at(oref1, ord1, s1, q1, (int)(y - p1), len1, c1, b1, x1);
+                    const bool differ = c0 != c1;
+                    if (differ) {
+                        const int cls = (c0 == 'N' || c1 == 'N') ? CONC_NOCALL
+                                        : (c0 == '-' || c1 == '-') ? CONC_INDEL : CONC_MISMATCH;
+                        conc_add(A, tkey, tval, cls, gb + (y - w0), 1);
+                        const int dq = (int)b0 - (int)b1;
+                        if (dq > -5 && dq < 5) conc_add(A, tkey, tval, CONC_UNRESOLVED, gb + (y - w0), 1);
+                    }
+                    if (x0 >= 0 && x1 >= 0 && c0 != 'N' && c1 != 'N') {
+                        const int cy0 = rev0 ? len0 - x0 : x0 + 1, cy1 = rev1 ? len1 - x1 : x1 + 1;
+                        if (cy0 < 1 || cy0 > A.max_len || cy1 < 1 || cy1 > A.max_len) {
+                            atomicExch(A.err, 1);
+                        } else {
+                            conc_read_add(A, rl, read0, cy0, differ);
+                            conc_read_add(A, rl, read0, A.max_len + 1 + b0, differ);
+                            conc_read_add(A, rl, read1, cy1, differ);
+                            conc_read_add(A, rl, read1, A.max_len + 1 + b1, differ);
+                        }
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();              // the next unit rewrites the op offsets
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < CONC_SLOTS; s += blockDim.x)
+        if (tkey[s] && tval[s]) atomicAdd(&A.acc[tkey[s] - 1ull], tval[s]);
+    for (int s = threadIdx.x; s < nrl; s += blockDim.x)
+        if (rl[s]) atomicAdd(&A.rd[s], (unsigned long long)rl[s]);
+}
+
+__global__ __launch_bounds__(1024) void k_s2a_conc_scan(const int64_t *base, const int32_t *wlen,
+                                                        int64_t total, const int32_t *acc,
+                                                        int32_t *idx_out, int32_t *cnt_out, int32_t *n_out)
+{
+    __shared__ int32_t wsum[16], wnz[16];
+    const int ref = blockIdx.x;
+    const int64_t b = base[ref];
+    const int n = wlen[ref] + 1;           // 0 for a reference without paired units (wlen -1)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int carry = 0, outn = 0;
+    for (int i0 = 0; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + (int)threadIdx.x;
+        const int v = i < n ? acc[b + i] : 0;
+        const int s = s2a_scan(v, lane);
+        if (lane == 63) wsum[wv] = s;
+        __syncthreads();
+        int pre = 0, tot = 0;
+        for (int w = 0; w < nw; ++w) { const int t = wsum[w]; pre += w < wv ? t : 0; tot += t; }
+        const int cov = carry + pre + s;
+        const int nz = i < n && cov != 0;
+        const int f = s2a_scan(nz, lane);
+        if (lane == 63) wnz[wv] = f;
+        __syncthreads();
+        int pre2 = 0, tot2 = 0;
+        for (int w = 0; w < nw; ++w) { const int t = wnz[w]; pre2 += w < wv ? t : 0; tot2 += t; }
+        if (nz) {
+            const int64_t k = b + outn + pre2 + f - 1;     // < b + n: one row per position at most
+            idx_out[k] = i;
+            cnt_out[k] = cov;
+#pragma unroll
+            for (int pl = 1; pl < CONC_PLANES; ++pl) cnt_out[pl * total + k] = acc[pl * total + b + i];
+        }
+        carry += tot;
+        outn += tot2;
+        __syncthreads();                   // wsum / wnz are rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) n_out[ref] = outn;
+}
+
+int s2a_conc_run(Ctx &c, S2AState &S)
+{
+    S2AConc &Q = S.conc;
+    if (Q.done) return 0;
+    if (S.clip.state == CLIP_NONE) {
+        set_error("sam2aln concordance: no rows of a sam2aln call are on the device");
+        return -3;
+    }
+    const S2ADevRows &rows = S.clip.rows;
+    if (S.n_merge && rows.cig != S.d_cig && (!c.map.valid || rows.cig != c.map.pool)) {
+        set_error("sam2aln concordance: the mapping pass the rows came from is gone");
+        return -3;
+    }
+    if (S.n_merge && rows.soff != S.d_soff && (rows.soff != c.reads.off || S.staged_reads != c.reads.n)) {
+        set_error("sam2aln concordance: the resident reads the rows came from are gone");
+        return -3;
+    }
+    Q.name.clear(); Q.pos.clear(); Q.count.clear(); Q.reads.clear();
+    Q.text_valid[0] = Q.text_valid[1] = false;
+    const int nref = (int)S.names.size();
+    const int64_t nu = (int64_t)S.u1.size();
+    // ---- per paired unit its orientation bits; each reference's window from
+    // its paired units' mapped intervals; the longest read and CIGAR ----
+    std::vector<uint8_t> orient((size_t)S.n_merge, 0);
+    std::vector<int64_t> lo((size_t)nref, INT64_MAX), hi((size_t)nref, INT64_MIN);
+    int max_len = 0, ops_cap = 1;
+    int64_t paired = 0, span_max = 1;
+    for (int64_t u = 0; S.n_merge && u < nu; ++u) {
+        if (S.ucause[u] >= 0 || !S.upaired[u] || S.u2[u] < 0) continue;
+        const int g = S.name_id[u];
+        int bits = 0, k = 0;
+        for (int64_t r : {S.u1[u], S.u2[u]}) {
+            // the read's length is its CIGAR's read bases, as the kernel takes it
+            // (S.slen holds it only for the rows insert.csv quotes on the resident route)
+            int64_t span = 0, bases = 0;
+            for (int o = 0; o < S.n_cig[r]; ++o) {
+                const uint32_t op = S.cig[S.cig_off[r] + o];
+                if ((op & 15) == MH_OP_M || (op & 15) == MH_OP_D) span += op >> 4;
+                if ((op & 15) != MH_OP_D) bases += op >> 4;
+            }
+            lo[g] = std::min(lo[g], (int64_t)S.pos[r]);
+            hi[g] = std::max(hi[g], (int64_t)S.pos[r] + span);
+            span_max = std::max(span_max, span);
+            max_len = (int)std::max<int64_t>(max_len, bases);
+            ops_cap = std::max(ops_cap, S.n_cig[r]);
+            bits |= (((S.flag[r] & 0x40) ? 0 : 1) | ((S.flag[r] & 0x10) ? 2 : 0)) << (2 * k++);
+        }
+        orient[(size_t)S.merge_of_unit[u]] = (uint8_t)bits;
+        ++paired;
+    }
+    std::vector<int64_t> base((size_t)nref + 1, 0);
+    std::vector<int32_t> wlen((size_t)nref, -1);
+    for (int g = 0; g < nref; ++g) {
+        if (lo[g] > hi[g]) { lo[g] = 0; base[g + 1] = base[g]; continue; }
+        if (hi[g] - lo[g] > S2A_CLIP_MAX_WINDOW) {
+            set_error("sam2aln concordance: the rows of %s span positions %lld to %lld, more than %lld",
+                      S.names[g].c_str(), (long long)lo[g], (long long)hi[g],
+                      (long long)S2A_CLIP_MAX_WINDOW);
+            return -3;
+        }
+        wlen[g] = (int32_t)(hi[g] - lo[g]);
+        base[g + 1] = base[g] + wlen[g] + 1;
+    }
+    const int64_t total = base[nref];
+    if (paired == 0 || total == 0) { Q.done = true; return 0; }
+    const int stride = max_len + 1 + 256;
+    const int rd_lds = stride <= CONC_READ_LDS ? 1 : 0;
+    const size_t rd_bytes = rd_lds ? (((size_t)4 * stride * 4 + 15) & ~(size_t)15) : 0;
+    const size_t wave_bytes = (size_t)16 * (ops_cap + 1);
+    int wpb = CONC_WPB;
+    while (wpb > 1 && rd_bytes + wpb * wave_bytes > S2A_LDS_BYTES - 16 * 1024) --wpb;
+    if (rd_bytes + wave_bytes > S2A_LDS_BYTES - 16 * 1024) {
+        set_error("sam2aln concordance: a read with %d CIGAR ops is too many for LDS", ops_cap);
+        return -3;
+    }
+    hipStream_t s = c.stream;
+    if (int st = s2a_upload(S, Q.d_orient, orient, s)) return st;
+    if (int st = s2a_upload(S, Q.d_lo, lo, s)) return st;
+    if (int st = s2a_upload(S, Q.d_base, base, s)) return st;
+    if (int st = s2a_upload(S, Q.d_wlen, wlen, s)) return st;
+    if (int st = dev_reserve(S, Q.d_acc, sizeof(int32_t) * CONC_PLANES * (size_t)total)) return st;
+    if (int st = dev_reserve(S, Q.d_idx, sizeof(int32_t) * (size_t)total)) return st;
+    if (int st = dev_reserve(S, Q.d_cnt, sizeof(int32_t) * CONC_PLANES * (size_t)total)) return st;
+    if (int st = dev_reserve(S, Q.d_n, sizeof(int32_t) * ((size_t)nref + 1))) return st;
+    if (int st = dev_reserve(S, Q.d_rd, sizeof(unsigned long long) * 4 * (size_t)stride)) return st;
+    MH_HIP(hipMemsetAsync(Q.d_acc, 0, sizeof(int32_t) * CONC_PLANES * (size_t)total, s));
+    MH_HIP(hipMemsetAsync(Q.d_n, 0, sizeof(int32_t) * ((size_t)nref + 1), s));
+    MH_HIP(hipMemsetAsync(Q.d_rd, 0, sizeof(unsigned long long) * 4 * (size_t)stride, s));
+    ConcArgs a{rows.seq, rows.qual, rows.soff, rows.pos, rows.cig_off, rows.n_cig, rows.cig,
+               S.d_units, S.d_uref, Q.d_orient, S.n_merge, Q.d_lo, Q.d_base, Q.d_wlen, total,
+               Q.d_acc, Q.d_rd, stride, max_len, rd_lds, ops_cap, Q.d_n + nref};
+    int64_t blocks = (S.n_merge + wpb * CONC_UNITS_PER_WAVE - 1) / (wpb * CONC_UNITS_PER_WAVE);
+    if (blocks > CONC_BLOCK_CAP) blocks = CONC_BLOCK_CAP;
+    // a block's 32-bit LDS sums stay below 2^31: a unit adds at most its overlap to one
+    // slot, and a block takes at most n_merge / blocks + wpb units
+    const int64_t need = (S.n_merge * span_max >> 30) + 1;
+    if (blocks < need) blocks = need;
+    const int64_t max_blocks = c.test_caps.s2a_max_blocks;
+    if (max_blocks > 0 && blocks > max_blocks && need <= max_blocks) blocks = max_blocks;
+    const size_t dyn = rd_bytes + wpb * wave_bytes;
+    MH_HIP(hipFuncSetAttribute((const void *)k_s2a_conc, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)dyn));
+    const int p0 = prof_begin(c, "k_s2a_conc");
+    hipLaunchKernelGGL(k_s2a_conc, dim3((unsigned)blocks), dim3(64 * wpb), dyn, s, a);
+    prof_end(c, p0);
+    MH_HIP(hipGetLastError());
+    const int p1 = prof_begin(c, "k_s2a_conc_scan");
+    hipLaunchKernelGGL(k_s2a_conc_scan, dim3((unsigned)nref), dim3(1024), 0, s, Q.d_base, Q.d_wlen, total,
+                       Q.d_acc, Q.d_idx, Q.d_cnt, Q.d_n);
+    prof_end(c, p1);
+    MH_HIP(hipGetLastError());
+    std::vector<int32_t> n_out((size_t)nref + 1);
+    std::vector<unsigned long long> rd((size_t)4 * stride);
+    MH_HIP(hipMemcpyAsync(n_out.data(), Q.d_n, sizeof(int32_t) * n_out.size(), hipMemcpyDeviceToHost, s));
+    MH_HIP(hipMemcpyAsync(rd.data(), Q.d_rd, sizeof(unsigned long long) * rd.size(),
+                          hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    prof_flush(c);
+    if (n_out[nref]) {
+        set_error("sam2aln concordance: a position or a cycle fell outside its table");
+        return -4;
+    }
+    // ---- the rows of each reference, references as Python sorts str ----
+    std::vector<int> order((size_t)nref);
+    for (int g = 0; g < nref; ++g) order[g] = g;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return S.names[x] < S.names[y]; });
+    std::vector<int64_t> at((size_t)nref + 1, 0);
+    for (int k = 0; k < nref; ++k) {
+        const int g = order[k];
+        if (n_out[g] < 0 || n_out[g] > wlen[g] + 1) {
+            set_error("sam2aln concordance: %d positions counted in a window of %d", n_out[g], wlen[g] + 1);
+            return -4;
+        }
+        at[k + 1] = at[k] + n_out[g];
+    }
+    const size_t nrow = (size_t)at[nref];
+    std::vector<int32_t> idx(nrow), planes(CONC_PLANES * nrow);
+    for (int k = 0; k < nref; ++k) {
+        const int g = order[k];
+        if (!n_out[g]) continue;
+        const size_t nb = sizeof(int32_t) * (size_t)n_out[g];
+        MH_HIP(hipMemcpyAsync(idx.data() + at[k], Q.d_idx + base[g], nb, hipMemcpyDeviceToHost, s));
+        for (int pl = 0; pl < CONC_PLANES; ++pl)
+            MH_HIP(hipMemcpyAsync(planes.data() + pl * nrow + at[k], Q.d_cnt + pl * total + base[g], nb,
+                                  hipMemcpyDeviceToHost, s));
+    }
+    MH_HIP(hipStreamSynchronize(s));
+    Q.name.resize(nrow);
+    Q.pos.resize(nrow);
+    Q.count.resize(CONC_PLANES * nrow);
+    for (int k = 0; k < nref; ++k)
+        for (int64_t j = at[k]; j < at[k + 1]; ++j) {
+            Q.name[j] = order[k];
+            Q.pos[j] = lo[order[k]] + idx[j];
+            for (int pl = 0; pl < CONC_PLANES; ++pl) Q.count[CONC_PLANES * j + pl] = planes[pl * nrow + j];
+        }
+    // ---- the read table's keys with compared > 0: read, then cycles, then qualities ----
+    for (int read = 0; read < 2; ++read)
+        for (int by = 0; by < 2; ++by) {
+            const int s0 = by ? max_len + 1 : 1, s1 = by ? stride : max_len + 1;
+            for (int sl = s0; sl < s1; ++sl) {
+                const unsigned long long cmp = rd[(size_t)read * stride + sl];
+                if (!cmp) continue;
+                const int64_t value = by ? sl - (max_len + 1) - 33 : sl;
+                Q.reads.insert(Q.reads.end(), {(int64_t)read + 1, (int64_t)by, value, (int64_t)cmp,
+                                               (int64_t)rd[(size_t)(2 + read) * stride + sl]});
+            }
+        }
+    Q.done = true;
+    return 0;
+}
+
+// concordance.csv (which 0) or cycle_concordance.csv (1) of S.conc's lists
+static void s2a_conc_text(S2AState &S, int which)
+{
+    S2AConc &Q = S.conc;
+    if (Q.text_valid[which]) return;
+    std::string &o = Q.text[which];
+    if (which == 0) {
+        o.assign("refname,pos,overlap,mismatch,indel,nocall,unresolved\n");
+        for (size_t j = 0; j < Q.name.size(); ++j) {
+            const std::string &rn = S.names[Q.name[j]];
+            csv_field(o, rn.data(), rn.size());
+            o.push_back(',');
+            o += std::to_string((long long)Q.pos[j]);
+            for (int pl = 0; pl < CONC_PLANES; ++pl) {
+                o.push_back(',');
+                o += std::to_string(Q.count[CONC_PLANES * j + pl]);
+            }
+            o.push_back('\n');
+        }
+    } else {
+        o.assign("read,by,value,compared,mismatch\n");
+        for (size_t j = 0; j + 4 < Q.reads.size(); j += 5) {
+            o += std::to_string((long long)Q.reads[j]);
+            o += Q.reads[j + 1] ? ",quality," : ",cycle,";
+            o += std::to_string((long long)Q.reads[j + 2]);
+            o.push_back(',');
+            o += std::to_string((long long)Q.reads[j + 3]);
+            o.push_back(',');
+            o += std::to_string((long long)Q.reads[j + 4]);
+            o.push_back('\n');
+        }
+    }
+    Q.text_valid[which] = true;
+}
+
+// the concordance of the context's last sam2aln call, counted now if not yet
+static int s2a_conc_of(mh_ctx *ctx, const char *what, int which, S2AState **out)
+{
+    Ctx &c = *ctx_of(ctx);
+    if (!c.s2a) { set_error("%s: no sam2aln results", what); return -3; }
+    if (which > 1) { set_error("%s: which must be 0 (positions) or 1 (reads)", what); return -3; }
+    MH_HIP(hipSetDevice(c.device));
+    try {
+        if (int st = s2a_conc_run(c, *c.s2a)) return st;
+        if (which >= 0) s2a_conc_text(*c.s2a, which);
+    } catch (const std::exception &e) {
+        c.s2a->conc.done = c.s2a->conc.text_valid[0] = c.s2a->conc.text_valid[1] = false;
+        set_error("%s: out of memory (%s)", what, e.what());
+        return -2;
+    }
+    *out = c.s2a;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Merged insertions (conseq_ins.csv; DESIGN.md section 6, "Merged
 // insertions").  Per read, walking the CIGAR with ref = POS - 1 and left = 0:
 // an I op of n > 0 bytes is the insertion (seq, qual)[left, left + n) at key
@@ -2098,6 +2585,55 @@ extern "C" int mh_sam2aln_clip_counts(mh_ctx *ctx, int32_t *name_id, int64_t *po
         memcpy(pos, K.pos.data(), sizeof(int64_t) * K.pos.size());
         memcpy(count, K.count.data(), sizeof(int32_t) * K.count.size());
     }
+    return 0;
+}
+
+extern "C" int mh_sam2aln_concordance(mh_ctx *ctx, int which, char *buf, size_t cap, size_t *used)
+{
+    if (!ctx || !used || which < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_conc_of(ctx, "mh_sam2aln_concordance", which, &S)) return st;
+    const std::string &t = S->conc.text[which];
+    *used = t.size();
+    if (!buf) return 0;
+    if (cap < t.size()) { set_error("mh_sam2aln_concordance: buffer too small"); return -2; }
+    memcpy(buf, t.data(), t.size());
+    return 0;
+}
+
+extern "C" int mh_sam2aln_concordance_write(mh_ctx *ctx, int which, int fd, int64_t offset,
+                                            int64_t *written)
+{
+    if (!ctx || which < 0 || fd < 0 || offset < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_conc_of(ctx, "mh_sam2aln_concordance_write", which, &S)) return st;
+    const std::string &t = S->conc.text[which];
+    if (const int e = write_all_at(fd, t.data(), t.size(), offset)) {
+        set_error("mh_sam2aln_concordance_write: write failed (%s)", strerror(e));
+        return -4;
+    }
+    if (written) *written = (int64_t)t.size();
+    return 0;
+}
+
+extern "C" int mh_sam2aln_conc_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *counts5,
+                                      int64_t cap, int64_t *n, int64_t *reads5, int64_t read_cap,
+                                      int64_t *read_n)
+{
+    if (!ctx || !n || !read_n || cap < 0 || read_cap < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_conc_of(ctx, "mh_sam2aln_conc_counts", -1, &S)) return st;
+    const S2AConc &Q = S->conc;
+    *n = (int64_t)Q.name.size();
+    *read_n = (int64_t)(Q.reads.size() / 5);
+    if (!name_id || !pos || !counts5 || !reads5) return 0;
+    if (cap < *n || read_cap < *read_n) { set_error("mh_sam2aln_conc_counts: buffer too small"); return -2; }
+    if (*n) {
+        memcpy(name_id, Q.name.data(), sizeof(int32_t) * Q.name.size());
+        memcpy(pos, Q.pos.data(), sizeof(int64_t) * Q.pos.size());
+        memcpy(counts5, Q.count.data(), sizeof(int32_t) * Q.count.size());
+    }
+    if (*read_n) memcpy(reads5, Q.reads.data(), sizeof(int64_t) * Q.reads.size());
     return 0;
 }
 

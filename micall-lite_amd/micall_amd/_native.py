@@ -152,6 +152,12 @@ def _declare(L):
                                  ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_clipping_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_clip_counts': ([_P, _P, _P, _P, ctypes.c_int64, _I64P], ctypes.c_int),
+        'mh_sam2aln_concordance': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_sam2aln_concordance_write': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _I64P],
+                                         ctypes.c_int),
+        'mh_sam2aln_conc_counts': ([_P, _P, _P, _P, ctypes.c_int64, _I64P, _P, ctypes.c_int64, _I64P],
+                                   ctypes.c_int),
         'mh_sam2aln_conseq_ins': ([_P, ctypes.c_char_p, ctypes.c_size_t,
                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_conseq_ins_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
@@ -716,6 +722,48 @@ class Context:
             check(lib().mh_sam2aln_clip_counts(self.h, _ptr(ids), _ptr(pos), _ptr(cnt), n.value,
                                                ctypes.byref(n)), 'mh_sam2aln_clip_counts')
         return ids, pos, cnt
+
+    def sam2aln_concordance(self, which):
+        """concordance.csv (which 0) or cycle_concordance.csv (which 1) text of
+        the last sam2aln call (mh_sam2aln_concordance): where the mates of the
+        paired units both align and how often they disagree, per consensus
+        position and per read cycle and quality.  The device pass runs on the
+        first request, once for both."""
+        used = ctypes.c_size_t()
+        check(lib().mh_sam2aln_concordance(self.h, int(which), None, 0, ctypes.byref(used)),
+              'mh_sam2aln_concordance')
+        buf = bytearray(used.value)
+        cbuf = (ctypes.c_char * len(buf)).from_buffer(buf)
+        check(lib().mh_sam2aln_concordance(self.h, int(which), cbuf, len(buf), ctypes.byref(used)),
+              'mh_sam2aln_concordance')
+        del cbuf
+        return buf.decode()
+
+    def sam2aln_concordance_write(self, which, fd, offset):
+        """The same text written to fd at offset (pwrite); bytes written."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_concordance_write(self.h, int(which), int(fd), int(offset), ctypes.byref(n)),
+              'mh_sam2aln_concordance_write')
+        return n.value
+
+    def sam2aln_conc_counts(self):
+        """(name ids int32, positions int64, counts int32 [rows, 5], reads
+        int64 [rows, 5]) of the two concordance files' rows
+        (mh_sam2aln_conc_counts): the counts are overlap, mismatch, indel,
+        nocall, unresolved; a reads row is read, by (0 cycle, 1 quality),
+        value, compared, mismatch.  Name ids as in sam2aln_clip_counts."""
+        n, rn = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().mh_sam2aln_conc_counts(self.h, None, None, None, 0, ctypes.byref(n), None, 0,
+                                           ctypes.byref(rn)), 'mh_sam2aln_conc_counts')
+        ids = np.empty(n.value, dtype=np.int32)
+        pos = np.empty(n.value, dtype=np.int64)
+        cnt = np.empty((n.value, 5), dtype=np.int32)
+        reads = np.empty((rn.value, 5), dtype=np.int64)
+        if n.value or rn.value:
+            check(lib().mh_sam2aln_conc_counts(self.h, _ptr(ids), _ptr(pos), _ptr(cnt), n.value,
+                                               ctypes.byref(n), _ptr(reads), rn.value, ctypes.byref(rn)),
+                  'mh_sam2aln_conc_counts')
+        return ids, pos, cnt, reads
 
     def sam2aln_conseq_ins(self):
         """conseq_ins.csv text of the last sam2aln call (mh_sam2aln_conseq_ins):

@@ -84,6 +84,7 @@ _SCHEMA = {
                   ['N', 'del', 'clip', 'coverage'],
     'nuc_detail_ins': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
                       ['N', 'del', 'clip', 'coverage', 'ins'],
+    'nuc_detail_conc': ['overlap', 'mismatch', 'indel'],     # appended with concordance_csv
     'amino_detail': ['seed', 'region', 'q-cutoff', 'query.aa.pos', 'refseq.aa.pos'] + list(AMINO_ALPHABET) +
                     ['X', 'partial', 'del', 'ins', 'clip', 'coverage'],
     'conseq': ['region', 'q-cutoff', 'consensus-percent-cutoff', 'offset', 'sequence'],
@@ -608,9 +609,13 @@ class SequenceReport(object):
     def write_amino_detail_header(self, amino_detail_file):
         _csv_writer(amino_detail_file, 'amino_detail').writeheader()
 
-    def write_nuc_detail_header(self, nuc_detail_file, insertions=False):
-        """insertions: the rows will end with the ins column."""
-        _csv_writer(nuc_detail_file, 'nuc_detail_ins' if insertions else 'nuc_detail').writeheader()
+    def write_nuc_detail_header(self, nuc_detail_file, insertions=False, concordance=False):
+        """insertions: the rows will end with the ins column; concordance:
+        with overlap, mismatch, indel after it."""
+        fields = _SCHEMA['nuc_detail_ins' if insertions else 'nuc_detail']
+        if concordance:
+            fields = fields + _SCHEMA['nuc_detail_conc']
+        csv.DictWriter(nuc_detail_file, fields, lineterminator=os.linesep).writeheader()
 
     # ---- bodies ----
     def _amino_lines(self):
@@ -698,7 +703,7 @@ class SequenceReport(object):
         positions when the seed has no coordinate region."""
         csv.writer(nuc_file, lineterminator=os.linesep).writerows(self._nuc_lines(4)[0])
 
-    def write_nuc_detail(self, nuc_detail_file, clipping=None, insertions=None):
+    def write_nuc_detail(self, nuc_detail_file, clipping=None, insertions=None, concordance=None):
         """nuc.csv's rows (not in the reference) followed by what they leave
         out: the N and deletion counts of the position, the units that
         soft-clip it, and coverage = A + C + G + T + N + del, the depth
@@ -709,8 +714,14 @@ class SequenceReport(object):
         insertions: {seed: {(q-cutoff, pos): count}} of sam2aln's
         conseq_ins.csv summed over the strings, None for no ins column; with
         it every row ends with ins, the units that carry an insertion after
-        the row's consensus position at the row's cutoff."""
+        the row's consensus position at the row's cutoff.  concordance:
+        {seed: {consensus position: (overlap, mismatch, indel)}} of sam2aln's
+        concordance.csv, None for none; with it every row ends (after ins)
+        with the pairs whose mates both align the row's consensus position and
+        those that disagree there on a base or on an indel, 0 without an
+        entry or a query position."""
         lines, frames = self._nuc_lines(6)
+        concs = None if concordance is None else concordance.get(self.seed, {})
         clips = None if clipping is None else clipping.get(self.seed, {})
         inserts = None if insertions is None else insertions.get(self.seed, {})
         for line, f in zip(lines, frames):
@@ -719,6 +730,8 @@ class SequenceReport(object):
             line[11:] = [clip, sum(line[5:11])]
             if inserts is not None:
                 line.append(0 if query == '' else inserts.get((int(self.qcut), query - f), 0))
+            if concs is not None:
+                line.extend((0, 0, 0) if query == '' else concs.get(query - f, (0, 0, 0)))
         csv.writer(nuc_detail_file, lineterminator=os.linesep).writerows(lines)
 
     def write_consensus(self, conseq_file, min_coverage=100):
@@ -1049,7 +1062,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
                coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
                nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None, linkage_csv=None,
-               linkage_positions=None, linkage_min_count=1):
+               linkage_positions=None, linkage_min_count=1, concordance_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -1061,6 +1074,9 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     clipping.csv (None: the column stays empty).  conseq_ins_csv is an input
     too, sam2aln's conseq_ins.csv: with it nuc_detail_csv's rows end with an
     ins column, the units that carry an insertion after the position.
+    concordance_csv is an input as well, sam2aln's concordance.csv: with it
+    nuc_detail_csv's rows end with overlap, mismatch and indel, the pairs
+    whose mates both align the position and those that disagree there.
     amino_detail_csv takes amino.csv's rows with the X, partial, del, ins, clip
     and coverage columns (SequenceReport.write_amino_detail): the codons read
     at the position that amino.csv leaves out, counted on the device only
@@ -1120,7 +1136,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             failed_align_csv, nuc_variants_csv, callback, coverage_summary_csv, json,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
                             nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv,
-                            amino_detail_csv=amino_detail_csv, linkage_csv=linkage_csv, link=link)
+                            amino_detail_csv=amino_detail_csv, linkage_csv=linkage_csv, link=link,
+                            concordance_csv=concordance_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -1130,7 +1147,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                         callback if stage.active else None, outs[6], json, groups=groups,
                         clipping_csv=clipping_csv, nuc_detail_csv=outs[8],
                         conseq_ins_csv=conseq_ins_csv, amino_detail_csv=outs[9], job_detail=job_detail,
-                        linkage_csv=None if job_link is None else outs[10] or io.StringIO(), link=job_link)
+                        linkage_csv=None if job_link is None else outs[10] or io.StringIO(), link=job_link,
+                        concordance_csv=concordance_csv)
         finally:
             _SHARD = None
 
@@ -1193,7 +1211,8 @@ def _load_sharded(sh, aligned_csv):
 def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv,
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
                 variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None,
-                amino_detail_csv=None, job_detail=False, linkage_csv=None, link=None):
+                amino_detail_csv=None, job_detail=False, linkage_csv=None, link=None,
+                concordance_csv=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -1217,8 +1236,9 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
         clipping = None if clipping_csv is None else _read_clipping(clipping_csv)
         insertions = None if conseq_ins_csv is None else _read_conseq_ins(conseq_ins_csv)
     if nuc_detail_csv is not None:
-        report.write_nuc_detail_header(nuc_detail_csv, insertions is not None)
-        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions))
+        concordance = None if concordance_csv is None else _read_concordance(concordance_csv)
+        report.write_nuc_detail_header(nuc_detail_csv, insertions is not None, concordance is not None)
+        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions, concordance))
     if amino_detail_csv is not None:
         report.write_amino_detail_header(amino_detail_csv)
         per_run.append(lambda: report.write_amino_detail(amino_detail_csv, clipping, insertions))
@@ -1289,6 +1309,15 @@ def _read_clipping(clipping_csv):
     return clipping
 
 
+def _read_concordance(concordance_csv):
+    """{refname: {pos: (overlap, mismatch, indel)}} of sam2aln's concordance.csv."""
+    concordance = {}
+    for row in csv.DictReader(concordance_csv):
+        concordance.setdefault(row['refname'], {})[int(row['pos'])] = (
+            int(row['overlap']), int(row['mismatch']), int(row['indel']))
+    return concordance
+
+
 def _read_conseq_ins(conseq_ins_csv):
     """{refname: {(qcut, pos): count summed over the strings}} of sam2aln's
     conseq_ins.csv."""
@@ -1318,6 +1347,9 @@ def _arguments(argv=None):
                      help="input: sam2aln's clipping.csv, for the clip column of the detail files")
     cli.add_argument('--conseq_ins_csv', type=argparse.FileType('r'),
                      help="input: sam2aln's conseq_ins.csv, for the ins column of the detail files")
+    cli.add_argument('--concordance_csv', type=argparse.FileType('r'),
+                     help="input: sam2aln's concordance.csv, for the overlap, mismatch and indel "
+                          "columns of nuc_detail_csv")
     cli.add_argument('--nuc_detail_csv', type=argparse.FileType('w'),
                      help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
     cli.add_argument('--amino_detail_csv', type=argparse.FileType('w'),
@@ -1341,7 +1373,7 @@ def main():
                clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv,
                conseq_ins_csv=a.conseq_ins_csv, amino_detail_csv=a.amino_detail_csv,
                linkage_csv=a.linkage_csv, linkage_positions=a.linkage_positions,
-               linkage_min_count=a.linkage_min_count)
+               linkage_min_count=a.linkage_min_count, concordance_csv=a.concordance_csv)
 
 
 if __name__ == '__main__':

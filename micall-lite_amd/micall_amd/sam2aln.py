@@ -45,6 +45,18 @@ and counted per distinct string: refname,qcut,pos,insert,count, pos the
 consensus position the insertion follows (not insert.csv's read-derived
 pos).  Counted on the device like the clipping (mh_sam2aln_conseq_ins:
 k_s2a_ins_rec, k_s2a_ins_merge, k_s2a_ins_tab), only when asked for.
+
+concordance_csv and cycle_concordance_csv (optional, not in the reference):
+what the merge sees and drops.  Over the paired units that reach the merge,
+whatever the q-cutoffs: per consensus position both mates align, the units
+(overlap) and those whose mates disagree there (mismatch, indel, nocall,
+and unresolved: qualities closer than 5, an N at every cutoff); and per
+read (1, 2) and sequencing cycle or reported quality, the bases compared
+with the mate's and found different -- the sample's own error estimate,
+with no phiX.  A cycle is the base's place in the read as the FASTQ held
+it, so after trim_fastqs it counts from the trimmed 5' end.  Counted on
+the device like the clipping (mh_sam2aln_concordance: k_s2a_conc,
+k_s2a_conc_scan), once for both files and only when asked for.
 """
 import argparse
 import os
@@ -78,14 +90,16 @@ def _cutoff_list(q_cutoffs):
 
 
 def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None,
-            clipping_csv=None, conseq_ins_csv=None):
+            clipping_csv=None, conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None):
     """sam2aln.sam2aln (sam2aln.py:395-478).  q_cutoffs: the list of quality
     cutoffs, None for the module's SAM2ALN_Q_CUTOFFS (where the reference's
     users set it).  In a sharded job every rank does its share
     (_sam2aln_sharded); when remap.csv cannot be split that way, rank 0
     computes and writes while the other ranks wait (session.writer_stage).
     clipping_csv: an open file for the soft-clip counts, None for none;
-    conseq_ins_csv: one for the merged insertions."""
+    conseq_ins_csv: one for the merged insertions; concordance_csv and
+    cycle_concordance_csv: one each for the mates' concordance per consensus
+    position and per read cycle and quality."""
     cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
@@ -93,10 +107,11 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     session.aligned_forget()     # recorded again below, once aligned.csv is these results
     use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
     if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts,
-                                           clipping_csv, conseq_ins_csv):
+                                           clipping_csv, conseq_ins_csv, concordance_csv,
+                                           cycle_concordance_csv):
         return
     with session.writer_stage(aligned_csv, insert_csv, failed_csv, clipping_csv,
-                              conseq_ins_csv) as stage:
+                              conseq_ins_csv, concordance_csv, cycle_concordance_csv) as stage:
         if not stage.active:
             return
         ctx = session.context()
@@ -118,6 +133,10 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
             _write_side(clipping_csv, ctx.sam2aln_clipping_write, ctx.sam2aln_clipping)
         if conseq_ins_csv:
             _write_side(conseq_ins_csv, ctx.sam2aln_conseq_ins_write, ctx.sam2aln_conseq_ins)
+        for which, handle in enumerate((concordance_csv, cycle_concordance_csv)):
+            if handle:
+                _write_side(handle, lambda fd, at, w=which: ctx.sam2aln_concordance_write(w, fd, at),
+                            lambda w=which: ctx.sam2aln_concordance(w))
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
                 start = _write_output(ctx, which, handle)
@@ -129,7 +148,7 @@ SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitter
 
 
 def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None, clipping_csv=None,
-                     conseq_ins_csv=None):
+                     conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None):
     """This rank's share of sam2aln.  False (on every rank, before any
     output is written) when the job must fall back to rank 0 alone: more
     than one q-cutoff (every rank holds the same list, so none has to ask),
@@ -163,6 +182,8 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
         _clipping_sharded(sh, ctx, names, clipping_csv)
     if conseq_ins_csv:
         _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv)
+    if concordance_csv or cycle_concordance_csv:
+        _concordance_sharded(sh, ctx, names, concordance_csv, cycle_concordance_csv)
     texts = sh.all_gather_bytes('\n'.join(names).encode())
     firsts = sh.all_gather_bytes(np.asarray(first, dtype=np.int64).tobytes())
     pairs = sh._gather_sizes([part['pair_units']])[:, 0]
@@ -209,7 +230,8 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
             o.finish()
     out.finish()
     sh.barrier()             # every rank's rows are in the files
-    for h in (aligned_csv, insert_csv, failed_csv, clipping_csv, conseq_ins_csv):
+    for h in (aligned_csv, insert_csv, failed_csv, clipping_csv, conseq_ins_csv, concordance_csv,
+              cycle_concordance_csv):
         if h and sh.rank == 0:
             h.flush()
     return True
@@ -237,6 +259,44 @@ def _clipping_sharded(sh, ctx, names, clipping_csv):
     w = csv.writer(clipping_csv, lineterminator='\n')
     w.writerow(['refname', 'pos', 'count'])
     w.writerows((name, p, total[name, p]) for name, p in sorted(total))
+
+
+CONCORDANCE_HEADER = ['refname', 'pos', 'overlap', 'mismatch', 'indel', 'nocall', 'unresolved']
+CYCLE_CONCORDANCE_HEADER = ['read', 'by', 'value', 'compared', 'mismatch']
+
+
+def _concordance_sharded(sh, ctx, names, concordance_csv, cycle_concordance_csv):
+    """The two concordance files of a sharded call: every rank counts the
+    paired units of its own rows on its device, the position rows and the
+    read tables are all-gathered, and rank 0 sums them and writes the files
+    that were asked for, as _clipping_sharded does."""
+    import csv
+    ids, pos, cnt, reads = ctx.sam2aln_conc_counts()
+    mine = '\n'.join(names).encode(), ids.tobytes(), pos.tobytes(), cnt.tobytes(), reads.tobytes()
+    parts = [sh.all_gather_bytes(x) for x in mine]
+    if sh.rank != 0:
+        return
+    total, table = {}, {}
+    for r in range(sh.world):
+        rn = parts[0][r].decode().split('\n') if parts[0][r] else []
+        for i, p, five in zip(np.frombuffer(parts[1][r], dtype=np.int32).tolist(),
+                              np.frombuffer(parts[2][r], dtype=np.int64).tolist(),
+                              np.frombuffer(parts[3][r], dtype=np.int32).reshape(-1, 5).tolist()):
+            key = rn[i], p
+            total[key] = [a + b for a, b in zip(total[key], five)] if key in total else five
+        for read, by, value, compared, mismatch in np.frombuffer(parts[4][r],
+                                                                 dtype=np.int64).reshape(-1, 5).tolist():
+            old = table.get((read, by, value), (0, 0))
+            table[read, by, value] = old[0] + compared, old[1] + mismatch
+    if concordance_csv:
+        w = csv.writer(concordance_csv, lineterminator='\n')
+        w.writerow(CONCORDANCE_HEADER)
+        w.writerows([name, p] + total[name, p] for name, p in sorted(total))
+    if cycle_concordance_csv:
+        w = csv.writer(cycle_concordance_csv, lineterminator='\n')
+        w.writerow(CYCLE_CONCORDANCE_HEADER)
+        w.writerows((read, 'quality' if by else 'cycle', value) + table[read, by, value]
+                    for read, by, value in sorted(table))
 
 
 def _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv):
@@ -324,6 +384,13 @@ def parseArgs():
     parser.add_argument('--conseq_ins_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
                         help='<output> CSV of the insertions left out of the consensus, merged per '
                              'pair and counted per consensus position and string')
+    parser.add_argument('--concordance_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
+                        help='<output> CSV of the positions both mates of a pair align: the pairs '
+                             'and how many disagree there (mismatch, indel, nocall, unresolved)')
+    parser.add_argument('--cycle_concordance_csv', type=argparse.FileType('w'), default=None,
+                        metavar='FILE',
+                        help='<output> CSV of the bases compared with the mate and found different, '
+                             'per read and sequencing cycle and per read and quality')
     return parser.parse_args()
 
 
@@ -331,7 +398,8 @@ def main():
     args = parseArgs()
     sam2aln(remap_csv=args.remap_csv, aligned_csv=args.aligned_csv, insert_csv=args.insert_csv,
             failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut,
-            clipping_csv=args.clipping_csv, conseq_ins_csv=args.conseq_ins_csv)
+            clipping_csv=args.clipping_csv, conseq_ins_csv=args.conseq_ins_csv,
+            concordance_csv=args.concordance_csv, cycle_concordance_csv=args.cycle_concordance_csv)
 
 
 if __name__ == '__main__':
