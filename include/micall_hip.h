@@ -711,7 +711,7 @@ int mh_censor_staged_write(mh_ctx *ctx, mh_fastq *fq, int n_bad, const char *con
                            const int32_t *cycles, int dst_gzip, int fd, int64_t offset,
                            int64_t *written, int64_t *base_count, int64_t *score_sum);
 /* Host wall ms of the last call: [0] gunzip + record split, [1] upload +
- * k_censor (+ k_trim, k_primer) + download, [2] rewrite + gzip. */
+ * k_censor (+ k_trim, k_primer, k_primer3) + download, [2] rewrite + gzip. */
 int mh_censor_timing(mh_ctx *ctx, double *ms3);
 /* 3' adapter trimming inside the censor pass (micall_amd.trim_fastqs; the
  * step bin/micall:133 names and does not have).  The adapters hold for this
@@ -762,6 +762,33 @@ int mh_censor_set_primers(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
  * k of direction d (0: read 1, 1: the others), bases[...] the bases they
  * lost at the front.  512 entries each; zero after mh_censor_set_primers. */
 int mh_censor_primer_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases);
+/* 3' primer trimming inside the censor pass (micall_amd.trim_fastqs): a read
+ * of an insert shorter than itself runs into the reverse complement of its
+ * mate's primer.  The primers hold for this context's following censor
+ * calls; n1 = n2 = 0 clears them.  seqs1 / seqs2 as for mh_censor_set_primers
+ * (0 to 256 primers each, 8 to 64 bases of ACGT), written as they read in
+ * the read.  max_errors[i], i = 0..64, is the number of errors allowed in i
+ * bases (0 <= max_errors[i] < max(i, 1)); min_overlap is 1 to 64.  Anything
+ * else: -3 and a message that names the primer or the table entry.
+ * After k_censor, k_trim and k_primer, k_primer3 compares x = r[lead:n] (n
+ * the kept length, lead k_primer's or 0; an 'N' matches nothing) with each
+ * primer p (m bases) of the record's direction, b being the bases cut from
+ * the end.  Full candidates: 1 <= b <= len(x) with F(b) <= max_errors[m],
+ * F(b) the least unit-cost edit distance between all of p and r[n-b:e] over
+ * e in n-b..n.  Partial candidates: min_overlap <= b <= min(len(x), m - 1)
+ * with G(b) <= max_errors[b], G(b) the least edit distance between p[:i] and
+ * all of r[n-b:n] over i in 0..m.  With L = m and D = F for a full, L = b and
+ * D = G for a partial candidate, the larger L - D wins, then the smaller D,
+ * the larger b, the lower primer index; the kept sequence and quality
+ * lengths are lowered to n - b.  A record cut to nothing stays as an empty
+ * record.  base_count / score_sum keep their meaning.  A record that keeps
+ * more than 65 535 bases fails the call as it does with adapters. */
+int mh_censor_set_primers3(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                           const char *const *seqs2, int min_overlap, const int32_t *max_errors);
+/* What the last censor call trimmed: reads[d * 256 + k] records won by 3'
+ * primer k of direction d (0: read 1, 1: the others), bases[...] the bases
+ * they lost at the end.  512 entries each; zero after mh_censor_set_primers3. */
+int mh_censor_primer3_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases);
 
 /* ---- aln2counts: replaces the per-read loops of aln2counts.py ---------- */
 /* aligned.csv text (refname, qcut, count, offset, seq columns) read as

@@ -25,6 +25,13 @@
 //             bit-vector edit distance (the primer's rows in one 64-bit
 //             word, one column per read base); the winner's end is the
 //             record's lead, the bases the writer drops at the front
+//   k_primer3 only with 3' primers set (mh_censor_set_primers3): one wave64
+//             per read, the same lanes and words, the read scanned from its
+//             last kept base backwards to its lead against the reversed
+//             primers, so that a column's index is the number of bases cut;
+//             a search state (the whole primer, starting at the cut) and a
+//             partial state (the read ends inside the primer) per lane; the
+//             winner lowers the record's kept lengths
 //   host      records rewritten (header and '+' lines verbatim) and, for
 //             gzip output, compressed, in blocks of ~8 MB of records on
 //             every host thread, sequence and quality lines from their lead
@@ -85,6 +92,16 @@ struct PrimerTab {
     uint64_t eq[2][4][PRIMER_MAX];
 };
 
+// the 3' primers as k_primer3 reads them: p.eq holds the masks of the
+// REVERSED primers (bit i set where the primer holds the base at m - 1 - i),
+// p.err the errors allowed in the whole primer, p.cols is not used;
+// max_err[b] is the budget of a partial match that removes b bases
+struct Primer3Tab {
+    PrimerTab p;
+    int32_t min_overlap;
+    int32_t max_err[PRIMER_MAXLEN + 1];
+};
+
 struct CensorState {
     TextBuf text;                           // the FASTQ (censored in place)
     // per record: line starts (header, seq, '+', qual); the header line is
@@ -124,6 +141,13 @@ struct CensorState {
     PrimerTab *d_primer = nullptr;
     int32_t *d_lead = nullptr;
     unsigned long long *d_pstat = nullptr;   // reads[512], bases[512]
+    // 3' primers of the following calls (mh_censor_set_primers3) and what the
+    // last call trimmed, per direction * PRIMER_MAX + primer
+    bool primer3_on = false;
+    std::unique_ptr<Primer3Tab> primer3;
+    int64_t primer3_reads[2 * PRIMER_MAX] = {}, primer3_bases[2 * PRIMER_MAX] = {};
+    Primer3Tab *d_primer3 = nullptr;
+    unsigned long long *d_p3stat = nullptr;  // reads[512], bases[512]
 };
 
 static void censor_free_device(CensorState &C)
@@ -134,6 +158,8 @@ static void censor_free_device(CensorState &C)
     C.d_trim = nullptr; C.d_tstat = nullptr;
     hipFree(C.d_primer); hipFree(C.d_lead); hipFree(C.d_pstat);
     C.d_primer = nullptr; C.d_lead = nullptr; C.d_pstat = nullptr;
+    hipFree(C.d_primer3); hipFree(C.d_p3stat);
+    C.d_primer3 = nullptr; C.d_p3stat = nullptr;
     C.d_text = nullptr; C.d_s0 = C.d_q0 = nullptr;
     C.d_sl = C.d_ql = C.d_tile = C.d_sign = C.d_keep = nullptr;
     C.d_bad = nullptr; C.d_sums = nullptr;
@@ -427,6 +453,154 @@ __global__ __launch_bounds__(256) void k_primer(PrimerArgs A)
         if (part[i]) atomicAdd(&A.stat[i], (unsigned long long)part[i]);
 }
 
+// ---- k_primer3: 3' primers --------------------------
+// The text is x = r[lead:n] (n the kept length, lead k_primer's or 0), the
+// pattern a primer p of m bases, b the bases cut from the end.  On the
+// reversed strings (q = p reversed, t = x reversed), column b of
+//   A: A[0][j] = 0, A[i][0] = i   F(b) = A[m][b]: all of p against r[n-b:e],
+//                                 the best e -- the primer starts at the cut
+//   B: B[0][j] = j, B[i][0] = 0   G(b) = B[m][b]: the best prefix of p against
+//                                 all of r[n-b:n] -- the read ends in the primer
+// Candidates are (k, b), 1 <= b <= len(x), with F(b) <= E[m] (L = m, D = F) and
+// (k, b), min_overlap <= b <= min(len(x), m - 1), with G(b) <= E[b] (L = b,
+// D = G); the larger L - D wins, then the smaller D, the larger b, the lower
+// primer index, which is the order of the 37-bit key
+//   (64 - (L - D)) << 30 | D << 24 | (65535 - b) << 8 | k
+// (1 <= L - D <= 64 and D < 64 as E[i] < i <= 64; b <= 65535).
+//
+// One wave per read, lane l takes the primers l, l + 64, ... as k_primer
+// does; every round of 64 primers scans the read again.  The scan runs from
+// the read's last kept base backwards: 64 bytes are loaded at a time in
+// reversed order, one block ahead, and each column's byte is broadcast from
+// the block in hand through an SGPR, so the column loop holds no load.  Both
+// states step on the same byte and the same mask of the reversed primer: A
+// with Myers' search boundary (pv = ~0, mv = 0, a horizontal delta of 0 into
+// row 0), B with pv = mv = 0 and a horizontal delta of +1 into row 0.  B can
+// hold a candidate only for b <= m - 1 <= 63, so it runs in the first
+// min(len(x), 63) columns alone.  Of a lane's full candidates the least F,
+// then the largest b, is the one its key can win with (m is the lane's own);
+// its partial candidates differ in L, so their order is kept in a 19-bit key
+// of the same fields.
+struct Primer3Args {
+    const uint8_t *text;
+    const int64_t *s0;
+    const int32_t *sign;
+    int64_t n;
+    int32_t *keep;
+    const int32_t *lead;        // null without 5' primers
+    const Primer3Tab *tab;
+    unsigned long long *stat;   // [slot] reads, [2 * PRIMER_MAX + slot] bases
+};
+
+__global__ __launch_bounds__(256) void k_primer3(Primer3Args A)
+{
+    constexpr int NS = 2 * PRIMER_MAX;
+    // what this block's reads lost, per slot (a cut is up to 65 535 bases)
+    __shared__ unsigned long long part[2 * NS];
+    for (int i = threadIdx.x; i < 2 * NS; i += blockDim.x) part[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const Primer3Tab &T = *A.tab;
+    const int min_ov = __builtin_amdgcn_readfirstlane(T.min_overlap);
+    // lane b: the budget of a partial match that removes b bases (b <= 63)
+    const int ev = T.max_err[lane];
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < A.n; r += (int64_t)gridDim.x * 4) {
+        const int dir = __builtin_amdgcn_readfirstlane(A.sign[r] == 1 ? 0 : 1);
+        const int n = __builtin_amdgcn_readfirstlane(A.keep[2 * r]);
+        const int np = __builtin_amdgcn_readfirstlane(T.p.n[dir]);
+        const int ld = A.lead ? min(max(__builtin_amdgcn_readfirstlane(A.lead[r]), 0), n) : 0;
+        const int len = n - ld;
+        // a longer read is left alone: the host fails the call for it
+        if (len <= 0 || n > TRIM_MAXREAD || np <= 0) continue;
+        // column b looks at end[-b]; lane l of block(p) holds column p + l + 1's byte
+        const uint8_t *end = A.text + A.s0[r] + n;
+        auto block = [&](int p) { return p + lane < len ? (uint32_t)end[-(p + lane) - 1] : 0u; };
+        const int cb = min(len, 63);
+        uint64_t best = ~0ull;
+        for (int k0 = 0; k0 < np; k0 += 64) {
+            const bool act = k0 + lane < np;
+            const int k = act ? k0 + lane : 0;
+            const int m = T.p.len[dir * PRIMER_MAX + k];
+            const uint64_t eq_a = T.p.eq[dir][0][k], eq_c = T.p.eq[dir][1][k];
+            const uint64_t eq_g = T.p.eq[dir][2][k], eq_t = T.p.eq[dir][3][k];
+            const uint64_t top = 1ull << (m - 1);
+            auto mask = [&](uint32_t c) {
+                return c == 'A' ? eq_a : c == 'C' ? eq_c : c == 'G' ? eq_g : c == 'T' ? eq_t : 0ull;
+            };
+            // A: lim is the least F so far, from the budget down; at: its last column
+            uint64_t pa = ~0ull, ma = 0;
+            int sa = m, lim = T.p.err[dir * PRIMER_MAX + k], at = 0;
+            auto column_a = [&](int b, uint64_t eq) {
+                const uint64_t xv = eq | ma;
+                const uint64_t xh = (((eq & pa) + pa) ^ pa) | eq;
+                uint64_t ph = ma | ~(xh | pa);
+                uint64_t mh = pa & xh;
+                sa += (ph & top ? 1 : 0) - (mh & top ? 1 : 0);
+                ph <<= 1;
+                mh <<= 1;
+                pa = mh | ~(xv | ph);
+                ma = ph & xv;
+                const bool hit = sa <= lim;
+                lim = hit ? sa : lim;
+                at = hit ? b : at;
+            };
+            // B: the least (64 - (b - G)) << 12 | G << 6 | (63 - b) over its candidates
+            uint64_t pb = 0, mb = 0;
+            int sb = 0;
+            uint32_t part_key = ~0u;
+            auto column_b = [&](int b, uint64_t eq, int budget) {
+                const uint64_t xv = eq | mb;
+                const uint64_t xh = (((eq & pb) + pb) ^ pb) | eq;
+                uint64_t ph = mb | ~(xh | pb);
+                uint64_t mh = pb & xh;
+                sb += (ph & top ? 1 : 0) - (mh & top ? 1 : 0);
+                ph = ph << 1 | 1ull;
+                mh <<= 1;
+                pb = mh | ~(xv | ph);
+                mb = ph & xv;
+                const uint32_t key = (uint32_t)(64 - (b - sb)) << 12 | (uint32_t)sb << 6 | (uint32_t)(63 - b);
+                part_key = min(part_key, b < m && sb <= budget ? key : ~0u);
+            };
+            uint32_t nxt = block(0);
+            for (int t0 = 0; t0 < len; t0 += 64) {
+                const uint32_t blk = nxt;
+                nxt = block(t0 + 64);
+                const int qn = min(64, len - t0);
+                int q = 0;
+                if (t0 == 0)
+                    for (; q < cb; ++q) {
+                        const uint64_t eq = mask((uint32_t)__builtin_amdgcn_readlane((int)blk, q));
+                        // below min_overlap no cost is within the budget
+                        const int budget = q + 1 >= min_ov ? __builtin_amdgcn_readlane(ev, q + 1) : -1;
+                        column_a(q + 1, eq);
+                        column_b(q + 1, eq, budget);
+                    }
+                for (; q < qn; ++q)
+                    column_a(t0 + q + 1, mask((uint32_t)__builtin_amdgcn_readlane((int)blk, q)));
+            }
+            if (act && at)
+                best = min(best, (uint64_t)(64 - (m - lim)) << 30 | (uint64_t)lim << 24 |
+                                     (uint64_t)(TRIM_MAXREAD - at) << 8 | (uint64_t)k);
+            if (act && part_key != ~0u)
+                best = min(best, (uint64_t)(part_key >> 6) << 24 |
+                                     (uint64_t)(TRIM_MAXREAD - 63 + (int)(part_key & 63u)) << 8 | (uint64_t)k);
+        }
+        for (int o = 32; o > 0; o >>= 1)
+            best = min(best, (uint64_t)__shfl_xor((unsigned long long)best, o, 64));
+        if (lane == 0 && best != ~0ull) {
+            const int b = TRIM_MAXREAD - (int)(best >> 8 & 0xffffu);
+            const int slot = dir * PRIMER_MAX + (int)(best & 255u);
+            A.keep[2 * r] = n - b;
+            A.keep[2 * r + 1] = min(A.keep[2 * r + 1], n - b);
+            atomicAdd(&part[slot], 1ull);
+            atomicAdd(&part[NS + slot], (unsigned long long)b);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * NS; i += blockDim.x)
+        if (part[i]) atomicAdd(&A.stat[i], part[i]);
+}
+
 
 // ---------------------------------------------------------------------------
 // host
@@ -539,6 +713,8 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     std::fill(std::begin(C.trim_bases), std::end(C.trim_bases), 0);
     std::fill(std::begin(C.primer_reads), std::end(C.primer_reads), 0);
     std::fill(std::begin(C.primer_bases), std::end(C.primer_bases), 0);
+    std::fill(std::begin(C.primer3_reads), std::end(C.primer3_reads), 0);
+    std::fill(std::begin(C.primer3_bases), std::end(C.primer3_bases), 0);
     C.lead.clear();
     if (nr == 0) return 0;
     if (C.primer_on) C.lead.assign((size_t)nr, 0);
@@ -592,6 +768,8 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     if (C.primer_on && !D.d_primer) H(hipMalloc(&D.d_primer, sizeof(PrimerTab)), "hipMalloc");
     if (C.primer_on && !D.d_pstat) H(hipMalloc(&D.d_pstat, pstat_bytes), "hipMalloc");
     if (C.primer_on && !D.d_lead) H(hipMalloc(&D.d_lead, 4 * D.cap_rec), "hipMalloc");
+    if (C.primer3_on && !D.d_primer3) H(hipMalloc(&D.d_primer3, sizeof(Primer3Tab)), "hipMalloc");
+    if (C.primer3_on && !D.d_p3stat) H(hipMalloc(&D.d_p3stat, pstat_bytes), "hipMalloc");
     if (st) { censor_free_device(D); return st; }
     H(hipMemcpyAsync(D.d_text, C.text.data(), C.text.size(), hipMemcpyHostToDevice, s), "H2D");
     H(hipMemcpyAsync(D.d_s0, C.s0.data(), 8 * nr, hipMemcpyHostToDevice, s), "H2D");
@@ -640,6 +818,21 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
         H(hipMemcpyAsync(pstat.data(), D.d_pstat, pstat_bytes, hipMemcpyDeviceToHost, s), "D2H");
         H(hipMemcpyAsync(C.lead.data(), D.d_lead, 4 * nr, hipMemcpyDeviceToHost, s), "D2H");
     }
+    std::vector<unsigned long long> p3stat;
+    if (C.primer3_on && !st) {   // on what the three passes before kept, behind k_primer's lead
+        p3stat.assign(2 * 2 * PRIMER_MAX, 0);
+        H(hipMemcpyAsync(D.d_primer3, C.primer3.get(), sizeof(Primer3Tab), hipMemcpyHostToDevice, s), "H2D");
+        H(hipMemsetAsync(D.d_p3stat, 0, pstat_bytes, s), "memset");
+        Primer3Args pa{D.d_text, D.d_s0, D.d_sign, nr, D.d_keep, C.primer_on ? D.d_lead : nullptr,
+                       D.d_primer3, D.d_p3stat};
+        if (!st) {
+            const int pk = prof_begin(c, "k_primer3");
+            hipLaunchKernelGGL(k_primer3, dim3((unsigned)blocks), dim3(256), 0, s, pa);
+            prof_end(c, pk);
+            H(hipGetLastError(), "k_primer3");
+        }
+        H(hipMemcpyAsync(p3stat.data(), D.d_p3stat, pstat_bytes, hipMemcpyDeviceToHost, s), "D2H");
+    }
     unsigned long long sums[2] = {0, 0};
     H(hipMemcpyAsync(C.text.data(), D.d_text, C.text.size(), hipMemcpyDeviceToHost, s), "D2H");
     H(hipMemcpyAsync(C.keep.data(), D.d_keep, 8 * nr, hipMemcpyDeviceToHost, s), "D2H");
@@ -649,9 +842,9 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
     prof_flush(c);
     C.score_sum = (long long)sums[0];
     C.base_count = (long long)sums[1];
-    if (C.trim_on) {
-        // k_trim leaves a read past its cap alone (its kept length is still
-        // k_censor's): such a read fails the call
+    if (C.trim_on || C.primer3_on) {
+        // k_trim and k_primer3 leave a read past their cap alone (its kept
+        // length is still k_censor's): such a read fails the call
         if (maxc > TRIM_MAXREAD)
             for (int64_t r = 0; r < nr; ++r)
                 if (C.keep[2 * r] > TRIM_MAXREAD) {
@@ -672,6 +865,11 @@ static int censor_run(Ctx &c, CensorState &C, const TileMap &tid, int n_bad, con
         for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
             C.primer_reads[k] = (int64_t)pstat[(size_t)k];
             C.primer_bases[k] = (int64_t)pstat[(size_t)(2 * PRIMER_MAX + k)];
+        }
+    if (C.primer3_on)
+        for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
+            C.primer3_reads[k] = (int64_t)p3stat[(size_t)k];
+            C.primer3_bases[k] = (int64_t)p3stat[(size_t)(2 * PRIMER_MAX + k)];
         }
     return 0;
 }
@@ -1061,6 +1259,72 @@ extern "C" int mh_censor_primer_stats(mh_ctx *ctx, int64_t *reads, int64_t *base
     for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
         reads[k] = c.censor ? c.censor->primer_reads[k] : 0;
         bases[k] = c.censor ? c.censor->primer_bases[k] : 0;
+    }
+    return 0;
+}
+
+extern "C" int mh_censor_set_primers3(mh_ctx *ctx, int n1, const char *const *seqs1, int n2,
+                                      const char *const *seqs2, int min_overlap,
+                                      const int32_t *max_errors)
+{
+    if (!ctx) return -3;
+    Ctx &c = *ctx_of(ctx);
+    if (!c.censor) c.censor = new CensorState();
+    CensorState &C = *c.censor;
+    std::fill(std::begin(C.primer3_reads), std::end(C.primer3_reads), 0);
+    std::fill(std::begin(C.primer3_bases), std::end(C.primer3_bases), 0);
+    if (n1 == 0 && n2 == 0) { C.primer3_on = false; return 0; }
+    if (min_overlap < 1 || min_overlap > PRIMER_MAXLEN) {
+        set_error("censor: 3' primer min_overlap %d is not in 1 to %d", min_overlap, PRIMER_MAXLEN);
+        return -3;
+    }
+    if (!max_errors) { set_error("censor: no error table"); return -3; }
+    std::unique_ptr<Primer3Tab> T(new Primer3Tab());
+    T->min_overlap = min_overlap;
+    for (int i = 0; i <= PRIMER_MAXLEN; ++i) {
+        // the fields of k_primer3's key: fewer than i errors in i bases
+        if (max_errors[i] < 0 || max_errors[i] >= std::max(i, 1)) {
+            set_error("censor: %d errors allowed in %d 3' primer bases", (int)max_errors[i], i);
+            return -3;
+        }
+        T->max_err[i] = max_errors[i];
+    }
+    const int n[2] = {n1, n2};
+    const char *const *seqs[2] = {seqs1, seqs2};
+    for (int d = 0; d < 2; ++d) {
+        if (n[d] < 0 || n[d] > PRIMER_MAX || (n[d] && !seqs[d])) {
+            set_error("censor: %d 3' primers for read direction %d (0 to %d)", n[d], d + 1, PRIMER_MAX);
+            return -3;
+        }
+        T->p.n[d] = n[d];
+        for (int k = 0; k < n[d]; ++k) {
+            const char *p = seqs[d][k];
+            const size_t m = p ? strnlen(p, PRIMER_MAXLEN + 1) : 0;
+            if (m < (size_t)PRIMER_MINLEN || m > (size_t)PRIMER_MAXLEN || strspn(p, "ACGT") != m) {
+                set_error("censor: 3' primer %d of read direction %d (%.70s) is not %d to %d bases of ACGT", k,
+                          d + 1, p ? p : "", PRIMER_MINLEN, PRIMER_MAXLEN);
+                return -3;
+            }
+            const int slot = d * PRIMER_MAX + k;
+            T->p.len[slot] = (int32_t)m;
+            T->p.err[slot] = max_errors[m];
+            // the scan runs backwards: row i of the column is base m - 1 - i
+            for (size_t i = 0; i < m; ++i)
+                T->p.eq[d][strchr("ACGT", p[m - 1 - i]) - "ACGT"][k] |= (uint64_t)1 << i;
+        }
+    }
+    C.primer3 = std::move(T);
+    C.primer3_on = true;
+    return 0;
+}
+
+extern "C" int mh_censor_primer3_stats(mh_ctx *ctx, int64_t *reads, int64_t *bases)
+{
+    if (!ctx || !reads || !bases) return -3;
+    Ctx &c = *ctx_of(ctx);
+    for (int k = 0; k < 2 * PRIMER_MAX; ++k) {
+        reads[k] = c.censor ? c.censor->primer3_reads[k] : 0;
+        bases[k] = c.censor ? c.censor->primer3_bases[k] : 0;
     }
     return 0;
 }

@@ -208,6 +208,9 @@ def _declare(L):
         'mh_censor_set_primers': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_char_p), _P], ctypes.c_int),
         'mh_censor_primer_stats': ([_P, _P, _P], ctypes.c_int),
+        'mh_censor_set_primers3': ([_P, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, _P], ctypes.c_int),
+        'mh_censor_primer3_stats': ([_P, _P, _P], ctypes.c_int),
         'mh_a2c_load_file': ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _I64P], ctypes.c_int),
         'mh_a2c_insert_rows': ([_P, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, _P, _P, ctypes.c_char_p,
                                 ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)],
@@ -910,6 +913,31 @@ class Context:
         each [direction][primer] (2 x 256) with direction 0 = read 1."""
         reads, bases = np.zeros(512, dtype=np.int64), np.zeros(512, dtype=np.int64)
         check(lib().mh_censor_primer_stats(self.h, _ptr(reads), _ptr(bases)), 'mh_censor_primer_stats')
+        return reads.reshape(2, 256).tolist(), bases.reshape(2, 256).tolist()
+
+    def censor_set_primers3(self, primers1, primers2, min_overlap, max_errors):
+        """mh_censor_set_primers3: 3' primers (str, as they read in the read)
+        of the records of read 1 / of all others for this context's following
+        censor calls, with max_errors[i], i = 0..64, errors allowed in i
+        bases and min_overlap the shortest partial match at the read's end;
+        two empty lists clear them."""
+        lists = []
+        for primers in (primers1, primers2):
+            lists.append((ctypes.c_char_p * max(len(primers), 1))(*[p.encode() for p in primers]))
+        if len(max_errors) != 65:
+            raise ValueError('max_errors holds {} entries, not 65'.format(len(max_errors)))
+        table = np.array(max_errors, dtype=np.int32)
+        check(lib().mh_censor_set_primers3(self.h, len(primers1), lists[0], len(primers2), lists[1],
+                                           int(min_overlap), _ptr(table)), 'mh_censor_set_primers3')
+
+    def censor_clear_primers3(self):
+        check(lib().mh_censor_set_primers3(self.h, 0, None, 0, None, 0, None), 'mh_censor_set_primers3')
+
+    def censor_primer3_stats(self):
+        """mh_censor_primer3_stats of the last censor call: (reads, bases),
+        each [direction][primer] (2 x 256) with direction 0 = read 1."""
+        reads, bases = np.zeros(512, dtype=np.int64), np.zeros(512, dtype=np.int64)
+        check(lib().mh_censor_primer3_stats(self.h, _ptr(reads), _ptr(bases)), 'mh_censor_primer3_stats')
         return reads.reshape(2, 256).tolist(), bases.reshape(2, 256).tolist()
 
     # ---- aln2counts -----------------------------------------------------

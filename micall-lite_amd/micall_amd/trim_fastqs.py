@@ -1,6 +1,6 @@
 """
-3' adapter trimming and anchored 5' primer trimming of a FASTQ file on the
-device, inside the censor pass:
+3' adapter trimming, anchored 5' primer trimming and 3' primer trimming of a
+FASTQ file on the device, inside the censor pass:
 the step the reference's chain names and does not have (bin/micall:133,
 "# TODO: add cutadapt step").  A sample is trimmed before the unchanged
 bin/micall runs on the result:
@@ -51,6 +51,31 @@ Caps: 256 primers per list, 8 to 64 bases of ACGT each (no IUPAC codes), whole
 primers at position 0 only; the read-length cap of the adapters does not
 apply.  No primer scheme is bundled: give a FASTA file, a {name: sequence}
 mapping or a list of sequences.
+
+3' primers (primers3_1 / primers3_2; k_primer3; tests/primer3_oracle.py
+restates the rules).  Where the insert is shorter than the read, read 1 runs
+through it into the reverse complement of the primer read 2 begins with, and
+read 2 into that of read 1's.  'mates' takes those reverse complements from
+this call's 5' lists (primers3_1='mates': of primers2; primers3_2='mates': of
+primers1); sequences given explicitly are written as they read in the read.
+Neither side defaults to the other.  The text is x = r[lead:n]: r as the
+passes before left it, n its kept length, lead the 5' pass's (0 without 5'
+primers).  For a 3' primer p of m bases and b bases cut from the end,
+  full     1 <= b <= len(x) with F(b) <= E[m], F(b) the least edit distance
+           between all of p and r[n-b:e] over e in n-b..n: the primer starts
+           at the cut and ends anywhere,
+  partial  primer3_min_overlap <= b <= min(len(x), m - 1) with G(b) <= E[b],
+           G(b) the least edit distance between p[:i] and all of r[n-b:n] over
+           i in 0..m: the read ends inside the primer;
+E is error_table(primer_error_rate).  With L = m for a full and L = b for a
+partial candidate the larger L - D wins, then the smaller D, the larger b,
+the lower primer index, and the sequence and quality lines keep n - b.
+
+Caps: those of the 5' primers, primer3_min_overlap from 1 to 64, and the
+adapters' read-length cap applies whenever a 3' list is set.
+
+    python -m micall_amd.trim_fastqs R1.fastq.gz R1.trimmed.fastq.gz --primers left.fasta \\
+        --primers2 right.fasta --primers3 mates --primers3-2 mates
 """
 import argparse
 import csv
@@ -154,19 +179,49 @@ def resolve_primers(primers1, primers2=None):
     return lists
 
 
+_COMPLEMENT = str.maketrans('ACGT', 'TGCA')
+
+
+def reverse_complement(seq):
+    return seq.translate(_COMPLEMENT)[::-1]
+
+
+def resolve_primers3(primers3_1, primers3_2, plists):
+    """(list for read 1, list for the other records) of (name, sequence) of
+    the 3' primers, as they read in the read.  Each side is None (no list),
+    the string 'mates' -- the reverse complements of the 5' list of the other
+    side (plists, as resolve_primers returned it), same order, same names --
+    or what resolve_primers takes; neither side defaults to the other."""
+    lists = []
+    for side, spec in enumerate((primers3_1, primers3_2)):
+        if isinstance(spec, str) and spec == 'mates':
+            mates = plists[1 - side]
+            if not mates:
+                raise ValueError("primers3_{} is 'mates' and primers{} is empty".format(side + 1, 2 - side))
+            lists.append([(name, reverse_complement(p)) for name, p in mates])
+        else:
+            # primers2=[] keeps resolve_primers from filling in the other side
+            lists.append(resolve_primers(spec, [])[0])
+    return tuple(lists)
+
+
 def trim(src, dest, adapters1, adapters2=None, bad_cycles_reader=(), use_gzip=True, summary_file=None,
          trim_summary_file=None, error_rate=0.1, min_overlap=3, primers1=None, primers2=None,
-         primer_error_rate=0.1, primer_summary_file=None):
+         primer_error_rate=0.1, primer_summary_file=None, primers3_1=None, primers3_2=None,
+         primer3_min_overlap=12, primer3_summary_file=None):
     """Censor src (bad_cycles_reader, as censor_fastq.censor), trim 3'
-    adapters and then anchored 5' primers (primers1 / primers2, as
-    resolve_primers takes them) in the same device pass, into dest; empty
+    adapters, then anchored 5' primers (primers1 / primers2, as
+    resolve_primers takes them) and then 3' primers (primers3_1 / primers3_2,
+    as resolve_primers3 takes them) in the same device pass, into dest; empty
     adapters with primers trim primers only.  summary_file gets the
     reference's censor summary, trim_summary_file one row per given adapter:
-    direction,adapter,reads,bases, primer_summary_file one row per given
-    primer: direction,name,primer,reads,bases.  Returns {'reads', 'bases',
+    direction,adapter,reads,bases, primer_summary_file and
+    primer3_summary_file one row per given primer:
+    direction,name,primer,reads,bases.  Returns {'reads', 'bases',
     'adapters': [the adapter rows as dicts], 'primer_reads', 'primer_bases',
-    'primers': [the primer rows as dicts]} (summed over the ranks of a sharded
-    job)."""
+    'primers': [the primer rows as dicts], 'primer3_reads', 'primer3_bases',
+    'primers3': [the 3' primer rows as dicts]} (summed over the ranks of a
+    sharded job)."""
     lists = resolve_adapters(adapters1, adapters2)
     if int(min_overlap) != min_overlap or min_overlap < 1:
         raise ValueError('min_overlap {!r} is not a whole number >= 1'.format(min_overlap))
@@ -174,19 +229,31 @@ def trim(src, dest, adapters1, adapters2=None, bad_cycles_reader=(), use_gzip=Tr
     plists = resolve_primers(primers1, primers2)
     ptable = error_table(primer_error_rate)
     with_primers = bool(plists[0] or plists[1])
+    p3lists = resolve_primers3(primers3_1, primers3_2, plists)
+    with_primers3 = bool(p3lists[0] or p3lists[1])
+    if isinstance(primer3_min_overlap, bool) or int(primer3_min_overlap) != primer3_min_overlap or \
+            not 1 <= primer3_min_overlap <= MAX_PRIMER:
+        raise ValueError('primer3_min_overlap {!r} is not a whole number from 1 to {}'.format(
+            primer3_min_overlap, MAX_PRIMER))
     ctx = session.context()
-    preads = pbases = [[0] * MAX_PRIMERS] * 2
+    preads = pbases = p3reads = p3bases = [[0] * MAX_PRIMERS] * 2
     try:
         ctx.censor_set_adapters(lists[0], lists[1], int(min_overlap), table)
         if with_primers:
             ctx.censor_set_primers([p for _, p in plists[0]], [p for _, p in plists[1]], ptable)
+        if with_primers3:
+            ctx.censor_set_primers3([p for _, p in p3lists[0]], [p for _, p in p3lists[1]],
+                                    int(primer3_min_overlap), ptable)
         censor_fastq.censor(src, bad_cycles_reader, dest, use_gzip=use_gzip, summary_file=summary_file)
         reads, bases = ctx.censor_trim_stats()
         if with_primers:
             preads, pbases = ctx.censor_primer_stats()
+        if with_primers3:
+            p3reads, p3bases = ctx.censor_primer3_stats()
     finally:
         ctx.censor_clear_adapters()
         ctx.censor_clear_primers()
+        ctx.censor_clear_primers3()
     sh = session.shard()
     if sh is not None:
         flat = [int(x) for x in sh.sum_i64(reads[0] + reads[1] + bases[0] + bases[1])]
@@ -195,10 +262,16 @@ def trim(src, dest, adapters1, adapters2=None, bad_cycles_reader=(), use_gzip=Tr
             n = MAX_PRIMERS
             flat = [int(x) for x in sh.sum_i64(preads[0] + preads[1] + pbases[0] + pbases[1])]
             preads, pbases = [flat[0:n], flat[n:2 * n]], [flat[2 * n:3 * n], flat[3 * n:4 * n]]
+        if with_primers3:
+            n = MAX_PRIMERS
+            flat = [int(x) for x in sh.sum_i64(p3reads[0] + p3reads[1] + p3bases[0] + p3bases[1])]
+            p3reads, p3bases = [flat[0:n], flat[n:2 * n]], [flat[2 * n:3 * n], flat[3 * n:4 * n]]
     rows = [dict(direction=d + 1, adapter=a, reads=reads[d][k], bases=bases[d][k])
             for d in (0, 1) for k, a in enumerate(lists[d])]
     prows = [dict(direction=d + 1, name=name, primer=p, reads=preads[d][k], bases=pbases[d][k])
              for d in (0, 1) for k, (name, p) in enumerate(plists[d])]
+    p3rows = [dict(direction=d + 1, name=name, primer=p, reads=p3reads[d][k], bases=p3bases[d][k])
+              for d in (0, 1) for k, (name, p) in enumerate(p3lists[d])]
     if trim_summary_file is not None and session.is_writer():
         writer = csv.DictWriter(trim_summary_file, ['direction', 'adapter', 'reads', 'bases'],
                                 lineterminator=os.linesep)
@@ -209,9 +282,16 @@ def trim(src, dest, adapters1, adapters2=None, bad_cycles_reader=(), use_gzip=Tr
                                 lineterminator=os.linesep)
         writer.writeheader()
         writer.writerows(prows)
+    if primer3_summary_file is not None and session.is_writer():
+        writer = csv.DictWriter(primer3_summary_file, ['direction', 'name', 'primer', 'reads', 'bases'],
+                                lineterminator=os.linesep)
+        writer.writeheader()
+        writer.writerows(p3rows)
     return dict(reads=sum(r['reads'] for r in rows), bases=sum(r['bases'] for r in rows), adapters=rows,
                 primer_reads=sum(r['reads'] for r in prows), primer_bases=sum(r['bases'] for r in prows),
-                primers=prows)
+                primers=prows,
+                primer3_reads=sum(r['reads'] for r in p3rows), primer3_bases=sum(r['bases'] for r in p3rows),
+                primers3=p3rows)
 
 
 def _adapter_arg(text):
@@ -221,6 +301,11 @@ def _adapter_arg(text):
 def _primer_arg(text):
     """--primers: a FASTA file if there is one of that name, else SEQ[,SEQ...]"""
     return text if os.path.exists(text) else [p for p in text.split(',') if p]
+
+
+def _primer3_arg(text):
+    """--primers3: 'mates', else as --primers"""
+    return text if text == 'mates' else _primer_arg(text)
 
 
 def main(argv=None):
@@ -244,9 +329,16 @@ def main(argv=None):
     ap.add_argument('--primers2', help='for the records that are not read 1 (default: --primers)')
     ap.add_argument('--primer-error-rate', type=float, default=0.1)
     ap.add_argument('--primer-summary', help='CSV of direction, name, primer, reads, bases')
+    ap.add_argument('--primers3', help="3' primers of the records of read 1, as they read in the read: "
+                                       "'mates' (the reverse complements of --primers2), FASTA file or "
+                                       "SEQ[,SEQ...]")
+    ap.add_argument('--primers3-2', help="3' primers of the records that are not read 1 ('mates': the "
+                                         "reverse complements of --primers); there is no default")
+    ap.add_argument('--primer3-min-overlap', type=int, default=12)
+    ap.add_argument('--primer3-summary', help="CSV of direction, name, primer, reads, bases of the 3' primers")
     args = ap.parse_args(argv)
-    if args.adapters is None and args.primers is None:
-        ap.error('one of --adapters and --primers is required')
+    if args.adapters is None and args.primers is None and args.primers3 is None and args.primers3_2 is None:
+        ap.error('one of --adapters, --primers and --primers3 is required')
     bad_cycles = []
     if args.bad_cycles:
         with open(args.bad_cycles) as f:
@@ -254,6 +346,7 @@ def main(argv=None):
     summary = open(args.summary, 'w') if args.summary else None
     trim_summary = open(args.trim_summary, 'w') if args.trim_summary else sys.stdout
     primer_summary = open(args.primer_summary, 'w') if args.primer_summary else None
+    primer3_summary = open(args.primer3_summary, 'w') if args.primer3_summary else None
     try:
         with open(args.src, 'rb') as src, open(args.dest, 'wb') as dest:
             trim(src, dest, () if args.adapters is None else _adapter_arg(args.adapters),
@@ -263,8 +356,13 @@ def main(argv=None):
                  min_overlap=args.min_overlap,
                  primers1=None if args.primers is None else _primer_arg(args.primers),
                  primers2=None if args.primers2 is None else _primer_arg(args.primers2),
-                 primer_error_rate=args.primer_error_rate, primer_summary_file=primer_summary)
+                 primer_error_rate=args.primer_error_rate, primer_summary_file=primer_summary,
+                 primers3_1=None if args.primers3 is None else _primer3_arg(args.primers3),
+                 primers3_2=None if args.primers3_2 is None else _primer3_arg(args.primers3_2),
+                 primer3_min_overlap=args.primer3_min_overlap, primer3_summary_file=primer3_summary)
     finally:
+        if primer3_summary is not None:
+            primer3_summary.close()
         if summary is not None:
             summary.close()
         if primer_summary is not None:
