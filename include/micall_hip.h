@@ -44,7 +44,9 @@
  *             regions (:346-375, :537-549) -> mh_a2c_variants; the codons
  *             count_aminos drops (:595-603) -> mh_a2c_codon_detail; the
  *             amino acids one read links at chosen positions (no
- *             counterpart in the reference) -> mh_a2c_link.
+ *             counterpart in the reference) -> mh_a2c_link; which minority
+ *             variants single reads carry together, every pair of up to 256
+ *             at once (no counterpart either) -> mh_a2c_gram.
  *
  * Conventions: every function returns 0 on success, -1 on traceback failure
  * (mh_gotoh_align only), -2 on out-of-memory, -3 on a bad argument, -4 on a
@@ -932,6 +934,29 @@ int mh_a2c_link_entries(mh_ctx *ctx, int slot, int32_t *set, int64_t *count, cha
  * the host; *ms (may be NULL) = host wall ms of the call, device work
  * included. */
 int mh_a2c_link_stats(mh_ctx *ctx, int slot, int64_t *coverage, int64_t *stats3, double *ms);
+/* Pairwise covariation (not in the reference): the weighted Gram matrix of
+ * n_cols (1 to 512) bit columns over the rows of group g.  Column i is read at
+ * consensus codon codon[i] (0-based) in reading frame frame[i] (0..2) and
+ * holds a row when the row's character there -- mh_a2c_link's, numbered 1..24
+ * in the order ACDEFGHIKLMNPQRSTVWY*X?- with 0 for a blank codon -- has its
+ * bit set in mask[i]: one bit for one character, 22 bits (the letters and
+ * '-') for "called".  gram[i * n_cols + j] = the summed count of the rows that
+ * columns i and j both hold: symmetric, returned in full, the diagonal a
+ * column's own count; exact in 64 bits.  Every row is read once for all
+ * columns (k_a2c_gram_bits: one bit per column and row, one classification
+ * per distinct (frame, codon)); the pairs are popcounts over the planes of the
+ * counts (k_a2c_gram_pairs).  A codon beyond the group's extent is legal:
+ * zeros.  After mh_a2c_part_count the rows are this rank's share, and the
+ * job's matrix is the sum of the ranks'.  -3: n_cols outside 1..512, a frame
+ * outside 0..2, a negative codon, a mask that is 0 or has bit 0 or a bit
+ * above 24 set, a slot without a load, no group g. */
+int mh_a2c_gram(mh_ctx *ctx, int slot, int64_t g, int n_cols, const int32_t *frame,
+                const int32_t *codon, const uint32_t *mask, int64_t *gram);
+/* Of the last mh_a2c_gram (zeros after a load or a refused call): stats[5] =
+ * rows of the group, 64-row words, planes of the counts that occur, distinct
+ * (frame, codon) classified, 64 x 64 tiles of pairs computed; *ms (may be
+ * NULL) = host wall ms of the call, device work included. */
+int mh_a2c_gram_stats(mh_ctx *ctx, int slot, int64_t *stats, double *ms);
 
 /* ---- aln2counts counting split over the ranks of a job (the same
  * aln2counts.py:115-172 loops; the counters are sums and a first row is a

@@ -50,6 +50,12 @@
 //                 this file): per (set of codons, row) the row's codon classes
 //                 at the set's codons as one exact key, grouped by
 //                 k_a2c_tab_count.
+//   k_a2c_gram_bits, k_a2c_gram_pairs
+//                 pairwise covariation (mh_a2c_gram, the last section of this
+//                 file): per column of the call one bit per row, "the row's
+//                 codon class here is in the column's mask", then the weighted
+//                 Gram matrix of the bit columns by popcount over the planes
+//                 of the row counts.
 // Host half (below the kernels): aligned.csv as csv.DictReader reads it,
 // consecutive (refname, qcut) groups (itertools.groupby, :884-887), the
 // codon extent of every frame, the bin lists.
@@ -161,6 +167,9 @@ struct A2CState {
     std::vector<int64_t> link_cov;            // per set of the call
     int64_t link_stats[3] = {0, 0, 0};        // pairs that counted, distinct entries, entries fetched
     double t_link = 0;
+    // figures of the last mh_a2c_gram: rows, row words, count planes, distinct (frame, codon), tiles
+    int64_t gram_stats[5] = {0, 0, 0, 0, 0};
+    double t_gram = 0;
     double t_parse = 0, t_count = 0, t_ins = 0;
     // a part of aligned.csv held between mh_a2c_part_open and _count (mapped)
     const char *part_text = nullptr;          // (null for an empty file)
@@ -1149,6 +1158,12 @@ static void a2c_clear_link(A2CState &S)
     S.t_link = 0;
 }
 
+static void a2c_clear_gram(A2CState &S)
+{
+    for (int k = 0; k < 5; ++k) S.gram_stats[k] = 0;
+    S.t_gram = 0;
+}
+
 static void a2c_clear_inserts(A2CState &S)
 {
     S.entries.clear();
@@ -1157,6 +1172,7 @@ static void a2c_clear_inserts(A2CState &S)
     S.var_region.clear();
     S.var_text.clear();
     a2c_clear_link(S);
+    a2c_clear_gram(S);
 }
 
 // The device memory of one call: every allocation is freed when the holder
@@ -2912,5 +2928,321 @@ extern "C" int mh_a2c_link_stats(mh_ctx *ctx, int slot, int64_t *coverage, int64
     if (coverage) for (size_t k = 0; k < S.link_cov.size(); ++k) coverage[k] = S.link_cov[k];
     for (int k = 0; k < 3; ++k) stats3[k] = S.link_stats[k];
     if (ms) *ms = S.t_link;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Pairwise covariation: the weighted Gram matrix of bit columns (the rule:
+// tests/covariation_oracle.py).  A column is (frame, codon, mask); it holds a
+// row when the row's linkage code there (1..24 of A2C_LINK_CHARS, 0 blank) has
+// its bit set in the mask.  gram[i][j] = the summed cnt of the rows both hold.
+//   k_a2c_gram_bits   lane = row, a wavefront per 64 consecutive rows of the
+//                     group (a row word).  The columns come sorted by (frame,
+//                     codon): every distinct site is classified once, as
+//                     k_a2c_link classifies (extent rejection before any byte
+//                     is read), and each of its columns is one mask test and
+//                     one __ballot.  Lane c % 64 keeps the ballot of column c,
+//                     so 64 columns of a word leave in one coalesced store:
+//                     bits[word][column], the layout k_a2c_gram_pairs stages.
+//                     The same ballots make the count planes,
+//                     planes[word][k] = bit k of cnt over the word's rows, and
+//                     the set of planes that occur at all.
+//   k_a2c_gram_pairs  a block owns a 64 x 64 tile of column pairs, on or above
+//                     the diagonal, and every gridDim.y-th slice of
+//                     A2C_GRAM_SLICE row words; the tile's 128 column slices
+//                     and the planes are staged in LDS, a thread holds a 4 x 4
+//                     block of pairs.  Per plane that occurs the thread sums
+//                     popcount(a & b & plane) over the slice in 32 bits, then
+//                     shifts the sum into its 64-bit accumulators; one 64-bit
+//                     atomicAdd per non-zero cell ends the block.  The host
+//                     mirrors the upper triangle.
+// ---------------------------------------------------------------------------
+namespace mh {
+
+constexpr int A2C_GRAM_MAX = 512;        // columns of a call
+constexpr int A2C_GRAM_SLICE = 32;       // row words of a slice: 2048 rows
+constexpr uint32_t A2C_GRAM_CODES = (1u << (A2C_LINK_DEL + 1)) - 2;   // bits 1..24
+
+struct A2CGramSite {
+    int32_t codon, frame, first, end;    // columns [first, end) of the sorted order read this site
+};
+
+struct A2CGramArgs {
+    const uint8_t *text;
+    const A2CRow *rows;
+    const int8_t *code;
+    const uint8_t *cls;
+    const A2CGramSite *sites;
+    const uint32_t *mask;                // per sorted column
+    int n_sites, n_cols, np;             // np: the columns padded to a multiple of 64
+    int64_t n_rows, n_words;
+    unsigned long long *bits;            // [n_words][np]
+    unsigned long long *planes;          // [n_words][32]
+    uint32_t *plane_set;                 // bit k: some row of the group has bit k of cnt
+    unsigned long long *gram;            // [np][np]
+};
+
+__global__ __launch_bounds__(256) void k_a2c_gram_bits(A2CGramArgs A)
+{
+    __shared__ int8_t s_code[512];
+    __shared__ uint8_t s_cls[256];
+    __shared__ A2CGramSite s_site[A2C_GRAM_MAX];
+    __shared__ uint32_t s_mask[A2C_GRAM_MAX];
+    s_code[threadIdx.x] = A.code[threadIdx.x];
+    s_code[threadIdx.x + 256] = A.code[threadIdx.x + 256];
+    s_cls[threadIdx.x] = A.cls[threadIdx.x];
+    for (int i = threadIdx.x; i < A.n_sites; i += 256) s_site[i] = A.sites[i];
+    for (int i = threadIdx.x; i < A.n_cols; i += 256) s_mask[i] = A.mask[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = (int64_t)gridDim.x * 4;
+    uint32_t seen = 0;                   // lane k < 32: plane k occurred in a word of this wave
+    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < A.n_words; w += n_waves) {
+        const int64_t r = w * 64 + lane;
+        const bool live = r < A.n_rows;
+        A2CRow R{0, 0, 0, 0, 0};
+        if (live) R = A.rows[r];
+        unsigned long long mine = 0;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            const unsigned long long b = __ballot((R.cnt >> k) & 1);
+            if (lane == k) mine = b;
+        }
+        if (lane < 32) {
+            A.planes[w * 32 + lane] = mine;
+            seen |= mine != 0;
+        }
+        const uint8_t *s = A.text + R.soff;
+        unsigned long long *out = A.bits + w * A.np;
+        mine = 0;
+        for (int i = 0; i < A.n_sites; ++i) {
+            const A2CGramSite L = s_site[i];
+            int k = 0;                                       // blank
+            // codons offset // 3 .. ceil((frame + offset + len) / 3) - 1 hold bytes of the row
+            if (live && L.codon >= R.off / 3 && L.codon < (L.frame + R.off + R.len + 2) / 3) {
+                const int q0 = 3 * L.codon - L.frame - R.off;
+                int c[3], inside = 0;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const int q = q0 + t;
+                    const bool in = q >= 0 && q < R.len;
+                    c[t] = in ? s_cls[s[q]] : A2C_DASH;
+                    inside += in;
+                }
+                const int a = s_code[64 * c[0] + 8 * c[1] + c[2]];
+                const int dashes = (c[0] == A2C_DASH) + (c[1] == A2C_DASH) + (c[2] == A2C_DASH);
+                const int bases = (c[0] < A2C_DASH) + (c[1] < A2C_DASH) + (c[2] < A2C_DASH);
+                if (a < A2C_NAA) k = a + 1;
+                else if (dashes == 3 && inside == 3) k = A2C_LINK_DEL;
+                else if (bases == 3) k = A2C_LINK_X;
+                else if (bases) k = A2C_LINK_PARTIAL;
+            }
+            for (int col = L.first; col < L.end; ++col) {    // wave-uniform
+                const unsigned long long b = __ballot((s_mask[col] >> k) & 1);   // no mask has bit 0
+                if (lane == (col & 63)) mine = b;
+                if ((col & 63) == 63) {
+                    out[col - 63 + lane] = mine;
+                    mine = 0;
+                }
+            }
+        }
+        // the last, partly filled 64 columns: zeros past n_cols
+        if (A.n_cols & 63) out[(A.n_cols & ~63) + lane] = mine;
+    }
+    if (lane < 32 && seen) atomicOr(A.plane_set, 1u << lane);
+}
+
+__global__ __launch_bounds__(256) void k_a2c_gram_pairs(A2CGramArgs A)
+{
+    __shared__ unsigned long long s_a[A2C_GRAM_SLICE][64], s_b[A2C_GRAM_SLICE][64], s_p[A2C_GRAM_SLICE][32];
+    // tile blockIdx.x of the upper triangle, rows of tiles first
+    const int side = A.np / 64;
+    int ti = 0, t = (int)blockIdx.x;
+    while (t >= side - ti) {
+        t -= side - ti;
+        ++ti;
+    }
+    const int tj = ti + t;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const uint32_t plane_set = *A.plane_set;
+    const int64_t n_slices = (A.n_words + A2C_GRAM_SLICE - 1) / A2C_GRAM_SLICE;
+    unsigned long long acc[4][4] = {};
+    for (int64_t sl = blockIdx.y; sl < n_slices; sl += gridDim.y) {
+        const int64_t w0 = sl * A2C_GRAM_SLICE;
+        __syncthreads();
+        for (int i = threadIdx.x; i < A2C_GRAM_SLICE * 64; i += 256) {
+            const int64_t w = w0 + (i >> 6);
+            const bool in = w < A.n_words;
+            s_a[i >> 6][i & 63] = in ? A.bits[w * A.np + 64 * ti + (i & 63)] : 0ull;
+            s_b[i >> 6][i & 63] = in ? A.bits[w * A.np + 64 * tj + (i & 63)] : 0ull;
+        }
+        for (int i = threadIdx.x; i < A2C_GRAM_SLICE * 32; i += 256) {
+            const int64_t w = w0 + (i >> 5);
+            s_p[i >> 5][i & 31] = w < A.n_words ? A.planes[w * 32 + (i & 31)] : 0ull;
+        }
+        __syncthreads();
+        for (uint32_t m = plane_set; m; m &= m - 1) {
+            const int k = __ffs((int)m) - 1;
+            // a slice is 64 * A2C_GRAM_SLICE = 2048 rows, so a plane's sum over it is at
+            // most 2048: 32 bits hold it.  Shifted by k <= 31 it is below 2^43, and a
+            // cell's total is at most the group's summed cnt, below 2^32 * 2^31 rows.
+            uint32_t part[4][4] = {};
+            for (int w = 0; w < A2C_GRAM_SLICE; ++w) {
+                const unsigned long long p = s_p[w][k];
+                unsigned long long b[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[j] = s_b[w][tx + 16 * j];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const unsigned long long a = s_a[w][ty + 16 * i] & p;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) part[i][j] += (uint32_t)__popcll(a & b[j]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] += (unsigned long long)part[i][j] << k;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (acc[i][j])
+                atomicAdd(&A.gram[(size_t)(64 * ti + ty + 16 * i) * A.np + 64 * tj + tx + 16 * j], acc[i][j]);
+}
+
+}  // namespace mh
+
+extern "C" int mh_a2c_gram(mh_ctx *ctx, int slot, int64_t g, int n_cols, const int32_t *frame,
+                           const int32_t *codon, const uint32_t *mask, int64_t *gram)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS) return -3;
+    Ctx &c = *ctx_of(ctx);
+    MH_HIP(hipSetDevice(c.device));
+    A2CState &S = *a2c_state(c, slot);
+    a2c_clear_gram(S);
+    if (n_cols < 1 || n_cols > A2C_GRAM_MAX) {
+        set_error("mh_a2c_gram: %d columns (1 .. %d)", n_cols, A2C_GRAM_MAX);
+        return -3;
+    }
+    if (!frame || !codon || !mask || !gram) return -3;
+    if (!S.counted) { set_error("mh_a2c_gram: nothing is loaded in slot %d", slot); return -3; }
+    const int64_t ng = (int64_t)S.g_first.size() - 1;
+    if (g < 0 || g >= ng) { set_error("mh_a2c_gram: no group %lld", (long long)g); return -3; }
+    for (int k = 0; k < n_cols; ++k) {
+        if (frame[k] < 0 || frame[k] > 2) { set_error("mh_a2c_gram: column %d: frame %d", k, frame[k]); return -3; }
+        if (codon[k] < 0) { set_error("mh_a2c_gram: column %d: negative codon", k); return -3; }
+        if (!mask[k] || (mask[k] & ~A2C_GRAM_CODES)) {
+            set_error("mh_a2c_gram: column %d: mask 0x%x (bits 1 .. %d, not 0)", k, mask[k], (int)A2C_LINK_DEL);
+            return -3;
+        }
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    const int64_t nr = S.g_first[g + 1] - S.g_first[g], nw = (nr + 63) / 64;
+    const int np = (n_cols + 63) / 64 * 64, side = np / 64, tiles = side * (side + 1) / 2;
+    memset(gram, 0, sizeof(int64_t) * (size_t)n_cols * n_cols);
+    int rc = 0;
+    try {
+        // the columns by (frame, codon): equal sites share one classification
+        std::vector<int> order(n_cols);
+        for (int k = 0; k < n_cols; ++k) order[k] = k;
+        std::sort(order.begin(), order.end(), [&](int x, int y) {
+            if (frame[x] != frame[y]) return frame[x] < frame[y];
+            if (codon[x] != codon[y]) return codon[x] < codon[y];
+            return x < y;
+        });
+        std::vector<A2CGramSite> sites;
+        std::vector<uint32_t> masks(n_cols);
+        for (int k = 0; k < n_cols; ++k) {
+            const int x = order[k];
+            masks[k] = mask[x];
+            if (k && frame[x] == frame[order[k - 1]] && codon[x] == codon[order[k - 1]]) sites.back().end = k + 1;
+            else sites.push_back({std::min(codon[x], A2C_LINK_FAR), frame[x], k, k + 1});
+        }
+        S.gram_stats[0] = nr;
+        S.gram_stats[1] = nw;
+        S.gram_stats[3] = (int64_t)sites.size();
+        S.gram_stats[4] = tiles;
+        if (nr) {
+            hipStream_t s = c.stream;
+            A2CDevMem mem;
+            A2CGramArgs a{};
+            A2CGramSite *d_sites;
+            uint32_t *d_mask;
+            hipError_t e = mem.alloc(d_sites, sites.size());
+            if (e == hipSuccess) e = mem.alloc(d_mask, masks.size());
+            if (e == hipSuccess) e = mem.alloc(a.bits, (size_t)nw * np);
+            if (e == hipSuccess) e = mem.alloc(a.planes, (size_t)nw * 32);
+            if (e == hipSuccess) e = mem.alloc(a.plane_set, 1);
+            if (e == hipSuccess) e = mem.alloc(a.gram, (size_t)np * np);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_sites, sites.data(), sizeof(A2CGramSite) * sites.size(), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_mask, masks.data(), sizeof(uint32_t) * masks.size(), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemsetAsync(a.plane_set, 0, sizeof(uint32_t), s);
+            if (e == hipSuccess) e = hipMemsetAsync(a.gram, 0, sizeof(unsigned long long) * np * np, s);
+            if (e != hipSuccess) {
+                a2c_clear_gram(S);
+                return hip_fail(e, "mh_a2c_gram alloc");
+            }
+            a.text = S.d_text;
+            a.rows = S.d_rows + S.g_first[g];
+            a.code = S.d_code;
+            a.cls = S.d_cls;
+            a.sites = d_sites;
+            a.mask = d_mask;
+            a.n_sites = (int)sites.size();
+            a.n_cols = n_cols;
+            a.np = np;
+            a.n_rows = nr;
+            a.n_words = nw;
+            const int64_t n_slices = (nw + A2C_GRAM_SLICE - 1) / A2C_GRAM_SLICE;
+            {
+                const int p0 = prof_begin(c, "k_a2c_gram_bits");
+                hipLaunchKernelGGL(k_a2c_gram_bits, dim3((unsigned)std::min<int64_t>((nw + 3) / 4, 8192)), dim3(256), 0, s, a);
+                prof_end(c, p0);
+                // about 2048 blocks: each tile's slices shared out over gridDim.y of them
+                const unsigned ny = (unsigned)std::min<int64_t>(n_slices, std::max(1, 2048 / tiles));
+                const int p1 = prof_begin(c, "k_a2c_gram_pairs");
+                hipLaunchKernelGGL(k_a2c_gram_pairs, dim3((unsigned)tiles, ny), dim3(256), 0, s, a);
+                prof_end(c, p1);
+            }
+            std::vector<unsigned long long> full((size_t)np * np);
+            uint32_t plane_set = 0;
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(full.data(), a.gram, sizeof(unsigned long long) * full.size(), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(&plane_set, a.plane_set, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = hip_fail(e, "k_a2c_gram");
+            S.gram_stats[2] = __builtin_popcount(plane_set);
+            // the upper triangle of the sorted order, mirrored, in the caller's order
+            for (int x = 0; x < n_cols && !rc; ++x)
+                for (int y = x; y < n_cols; ++y) {
+                    const int64_t v = (int64_t)full[(size_t)x * np + y];
+                    gram[(size_t)order[x] * n_cols + order[y]] = v;
+                    gram[(size_t)order[y] * n_cols + order[x]] = v;
+                }
+        }
+    } catch (const std::exception &ex) {
+        set_error("mh_a2c_gram: out of memory (%s)", ex.what());
+        rc = -2;
+    }
+    prof_flush(c);
+    const double t = ms_since(t0);
+    if (rc) {
+        a2c_clear_gram(S);
+        memset(gram, 0, sizeof(int64_t) * (size_t)n_cols * n_cols);
+    }
+    S.t_gram = t;
+    return rc;
+}
+
+extern "C" int mh_a2c_gram_stats(mh_ctx *ctx, int slot, int64_t *stats, double *ms)
+{
+    if (!ctx || slot < 0 || slot >= A2C_SLOTS || !stats) return -3;
+    Ctx &c = *ctx_of(ctx);
+    A2CState &S = *a2c_state(c, slot);
+    for (int k = 0; k < 5; ++k) stats[k] = S.gram_stats[k];
+    if (ms) *ms = S.t_gram;
     return 0;
 }

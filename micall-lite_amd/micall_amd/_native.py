@@ -239,6 +239,8 @@ def _declare(L):
         'mh_a2c_link_entries': ([_P, ctypes.c_int, _P, _P, ctypes.c_char_p, ctypes.c_size_t,
                                  ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_a2c_link_stats': ([_P, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'mh_a2c_gram': ([_P, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P], ctypes.c_int),
+        'mh_a2c_gram_stats': ([_P, ctypes.c_int, _P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         'mh_fastq_open_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 ctypes.POINTER(_P), _I64P], ctypes.c_int),
         'mh_fastq_scan_part': ([ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I64P],
@@ -1215,6 +1217,38 @@ class Context:
         stats['coverage'] = [int(x) for x in cov[:len(sets)]]
         stats['ms'] = ms.value
         return [(int(which[i]), int(cnt[i]), haps[i]) for i in range(k)], stats
+
+    GRAM_STATS = ('rows', 'words', 'planes', 'sites', 'tiles')
+    GRAM_MAX_COLUMNS = 512
+
+    def a2c_gram(self, slot, g, cols):
+        """mh_a2c_gram over group g for cols = [(frame, consensus codon,
+        mask)]: column i holds a row when the row's character at (frame,
+        codon) -- code 1..24 in the order ACDEFGHIKLMNPQRSTVWY*X?-, 0 blank --
+        has its bit set in mask.  Returns ((n, n) int64 array, the summed
+        count of the rows both columns hold; stats dict of GRAM_STATS plus
+        'ms')."""
+        cols = [(int(f), int(k), int(m)) for f, k, m in cols]
+        n = len(cols)
+        if any(not 0 <= m < 2 ** 32 for _f, _k, m in cols):
+            raise NativeError('mh_a2c_gram: a mask outside 32 bits')
+        frames = np.array([c[0] for c in cols] or [0], dtype=np.int32)
+        codons = np.array([c[1] for c in cols] or [0], dtype=np.int32)
+        masks = np.array([c[2] for c in cols] or [0], dtype=np.uint32)
+        gram = np.zeros((max(n, 1), max(n, 1)), dtype=np.int64)
+        check(lib().mh_a2c_gram(self.h, slot, g, n, _ptr(frames), _ptr(codons), _ptr(masks), _ptr(gram)),
+              'mh_a2c_gram')
+        return gram, self.a2c_gram_stats(slot)
+
+    def a2c_gram_stats(self, slot):
+        """The figures of the slot's last a2c_gram: zeros after a load or a
+        refused call."""
+        st = np.zeros(len(self.GRAM_STATS), dtype=np.int64)
+        ms = ctypes.c_double()
+        check(lib().mh_a2c_gram_stats(self.h, slot, _ptr(st), ctypes.byref(ms)), 'mh_a2c_gram_stats')
+        stats = dict(zip(self.GRAM_STATS, (int(x) for x in st)))
+        stats['ms'] = ms.value
+        return stats
 
     def a2c_timing(self, slot):
         out = np.zeros(3, dtype=np.float64)

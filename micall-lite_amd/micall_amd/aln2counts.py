@@ -42,6 +42,12 @@ unchanged.  Differences that never reach an output file:
     region, a report the reference does not have, are counted only when asked
     for (SequenceReport.count_linkage / write_linkage, aln2counts(linkage_csv=,
     linkage_positions=), --linkage_csv): k_a2c_link through mh_a2c_link;
+  * which minority variants single reads carry together or keep apart, every
+    pair of the variants a run's own counts select, another report the
+    reference does not have, is counted only when asked for
+    (SequenceReport.count_covariation / write_covariation,
+    aln2counts(covariation_csv=), --covariation_csv): k_a2c_gram_bits and
+    k_a2c_gram_pairs through mh_a2c_gram;
   * an InsertionWriter fed by a SequenceReport reads the run's rows from the
     device, so its nuc_seqs stays empty;
   * characters other than A C G T N - n, negative offsets and counts of 2**32
@@ -93,8 +99,18 @@ _SCHEMA = {
     'insert': ['seed', 'region', 'qcut', 'left', 'insert', 'count', 'before'],
     'coverage': ['avg_coverage', 'coverage_region', 'region_width'],
     'linkage': ['seed', 'region', 'q-cutoff', 'positions', 'haplotype', 'count', 'coverage'],
+    'covariation': ['seed', 'q-cutoff', 'region.a', 'pos.a', 'aa.a', 'region.b', 'pos.b', 'aa.b', 'n', 'n.a',
+                    'n.b', 'n.ab', 'direction', 'r2'],
 }
 LINKAGE_MAX_POSITIONS = 12            # positions of one linked set (mh_a2c_link: 5 key bits each)
+
+# Covariation: the called characters of a codon in character order (the 21
+# letters, then del), the bit of each in a column mask of mh_a2c_gram (codes
+# 1..21 the letters, 24 del) and the mask of all of them.
+COVARIATION_CALLED = AMINO_ALPHABET + '-'
+COVARIATION_MAX_VARIANTS = 256        # two columns each at most: mh_a2c_gram takes 512
+_COVAR_BIT = [1 << (k + 1) for k in range(len(AMINO_ALPHABET))] + [1 << 24]
+_COVAR_CALLED = sum(_COVAR_BIT)
 
 SLOT_REPORT, SLOT_INSERTS = 0, 1      # device row tables (mh_a2c slots) used here
 _CODON_CHARS = codon_chars()
@@ -368,6 +384,37 @@ def _check_linkage(positions, min_count=1):
     return checked
 
 
+def _check_covariation(min_fraction=0.01, min_count=10, max_variants=COVARIATION_MAX_VARIANTS):
+    """The thresholds of a covariation report as (min_fraction, min_count,
+    max_variants); ValueError naming the one that is out of range:
+    min_fraction outside (0, 1], min_count < 1, max_variants outside 1 ..
+    256.  No device is touched."""
+    if (isinstance(min_fraction, bool) or not isinstance(min_fraction, (int, float, np.integer, np.floating)) or
+            not 0 < min_fraction <= 1):
+        raise ValueError('covariation: min_fraction must be a number in (0, 1], not %r' % (min_fraction,))
+    for name, value, top in (('min_count', min_count, None), ('max_variants', max_variants,
+                                                              COVARIATION_MAX_VARIANTS)):
+        if (isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1 or
+                (top is not None and value > top)):
+            raise ValueError('covariation: %s must be an integer %s, not %r' %
+                             (name, '>= 1' if top is None else 'in 1 .. %d' % top, value))
+    return float(min_fraction), int(min_count), int(max_variants)
+
+
+def covariation_direction(n, na, nb, nab):
+    """'+', '-' or '0': the two variants share rows more often, less often
+    or exactly as often as independent ones would."""
+    return '+' if n * nab > na * nb else '-' if n * nab < na * nb else '0'
+
+
+def covariation_r2(n, na, nb, nab):
+    """The squared correlation of the two indicators over the n rows called
+    at both codons as '%.4f': integer numerator and denominator, one
+    division; '' when a margin is empty or full."""
+    bottom = na * (n - na) * nb * (n - nb)
+    return '' if bottom == 0 else '%.4f' % ((n * nab - na * nb) ** 2 / bottom)
+
+
 def _load_linkage(positions):
     """linkage_positions of aln2counts(): the mapping itself, or the path of
     a JSON file that holds only that mapping."""
@@ -473,6 +520,7 @@ class SequenceReport(object):
         self._job_detail = None
         self.linkage_unplaced = []
         self.linkage_stats = None
+        self.covariation_stats = None
         if run is not None:
             self.seed, self.qcut = run.seed, run.qcut
             self.insert_writer.start_group(run.seed, run.qcut)
@@ -864,6 +912,102 @@ class SequenceReport(object):
             where = ';'.join(str(p) for p in chosen)
             out.writerows([self.seed, name, self.qcut, where, hap, count, coverage] for hap, count in found)
 
+    def write_covariation_header(self, covariation_file):
+        _csv_writer(covariation_file, 'covariation').writeheader()
+
+    def _covariation_candidates(self, min_fraction, min_count):
+        """Every variant of the run as (-tally, region, position, character
+        index, frame, consensus codon), from the tables the reports are made
+        of: amino.csv's 21 counts and amino_detail.csv's del."""
+        found = []
+        for name in sorted(getattr(self, 'reports', {})):
+            cmap = self._coord_maps.get(name)
+            if cmap is None or not len(cmap):        # no reading frame aligned to it
+                continue
+            f = cmap.frame
+            letters = self._gather(cmap, lambda fr: fr.aa_cnt, (len(AMINO_ALPHABET),))
+            dels = self._gather(cmap, lambda fr: self._codon_detail(f), (3,))[:, 2]
+            for tally, t_del, k, pos in zip(letters.tolist(), dels.tolist(), cmap.conseq_index.tolist(),
+                                            cmap.positions.tolist()):
+                tally.append(t_del)
+                called = sum(tally)
+                if k < 0 or not called:
+                    continue
+                major = tally.index(max(tally))      # ties: the earlier character
+                found.extend((-t, name, pos, c, f, k) for c, t in enumerate(tally)
+                             if c != major and t >= min_count and t >= min_fraction * called)
+        return found
+
+    def count_covariation(self, min_fraction=0.01, min_count=10, max_variants=COVARIATION_MAX_VARIANTS):
+        """Which minority variants of the run just read travel together on
+        single reads (not in the reference).  A row's character at a position
+        is linkage's; the 21 letters and '-' (del) are *called*.  Per
+        coordinate position with a consensus codon the major is the called
+        character with the largest summed count (ties: the earlier of
+        COVARIATION_CALLED); every other called character counted at least
+        min_count times and at least min_fraction of the position's called
+        rows is a variant.  More than max_variants (at most 256): the most
+        counted stay, ties by (region name, position, character order), and
+        covariation_stats['dropped'] says how many went.
+
+        Returns one record per pair a < b of the kept variants, ordered by
+        (region name, position, character order), that sit on different
+        (frame, consensus codon) -- two regions of one seed pair up too --
+        and have n >= min_count: (region.a, pos.a, aa.a, region.b, pos.b,
+        aa.b, n, n.a, n.b, n.ab), over the rows called at both codons their
+        summed count and those carrying a's character, b's, and both.
+
+        The variants come from the tables amino.csv and amino_detail.csv are
+        made of (in a sharded job the job's); the pairs from one device call
+        (mh_a2c_gram; its figures in covariation_stats['native']) with one
+        "called" column per distinct codon and one column per variant, made
+        only when asked and only when two variants are kept.  In a sharded job
+        every rank computes the matrix of its own rows and the matrices are
+        added."""
+        min_fraction, min_count, max_variants = _check_covariation(min_fraction, min_count, max_variants)
+        self.covariation_stats = dict(variants=0, dropped=0, columns=0, pairs=0, native=None)
+        run = getattr(self, '_run', None)
+        if run is None:
+            return []
+        found = sorted(self._covariation_candidates(min_fraction, min_count))
+        kept = sorted(v[1:] for v in found[:max_variants])
+        self.covariation_stats.update(variants=len(kept), dropped=len(found) - len(kept))
+        if len(kept) < 2:
+            return []
+        site = {}
+        for _name, _pos, _c, f, k in kept:
+            site.setdefault((f, k), len(site))
+        cols = [(f, k, _COVAR_CALLED) for f, k in site] + [(f, k, _COVAR_BIT[c]) for _n, _p, c, f, k in kept]
+        if _SHARD is not None and run.slot == SLOT_REPORT:
+            from .sharded_io import _checked
+            mine, native = _checked(_SHARD, lambda: run.ctx.a2c_gram(run.slot, run.group, cols))
+            gram = sum(np.frombuffer(blob, dtype='<i8').reshape(len(cols), len(cols))
+                       for blob in _SHARD.all_gather_bytes(mine.astype('<i8').tobytes()))
+        else:
+            gram, native = run.ctx.a2c_gram(run.slot, run.group, cols)
+        gram = gram.tolist()
+        out = []
+        for i, a in enumerate(kept):
+            sa, va = site[a[3:]], len(site) + i
+            for j in range(i + 1, len(kept)):
+                b = kept[j]
+                sb, vb = site[b[3:]], len(site) + j
+                n = gram[sa][sb]
+                if sa != sb and n >= min_count:
+                    out.append((a[0], a[1], COVARIATION_CALLED[a[2]], b[0], b[1], COVARIATION_CALLED[b[2]],
+                                n, gram[va][sb], gram[sa][vb], gram[va][vb]))
+        self.covariation_stats.update(columns=len(cols), pairs=len(out), native=native)
+        return out
+
+    def write_covariation(self, covariation_file, min_fraction=0.01, min_count=10,
+                          max_variants=COVARIATION_MAX_VARIANTS):
+        """covariation.csv's rows of this run: per pair (count_covariation)
+        the four counts, direction ('+', '-' or '0' as n * n.ab is above,
+        below or equal to n.a * n.b) and r2."""
+        out = csv.writer(covariation_file, lineterminator=os.linesep)
+        out.writerows([self.seed, self.qcut] + list(r) + [covariation_direction(*r[6:]), covariation_r2(*r[6:])]
+                      for r in self.count_covariation(min_fraction, min_count, max_variants))
+
     def write_failure(self, fail_file):
         """One row per coordinate region that no reading frame aligned to."""
         out = _csv_writer(fail_file, 'failed')
@@ -1062,7 +1206,9 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                failed_align_csv=None, nuc_variants_csv=None, callback=None,
                coverage_summary_csv=None, json=None, variants_csv=None, clipping_csv=None,
                nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None, linkage_csv=None,
-               linkage_positions=None, linkage_min_count=1, concordance_csv=None):
+               linkage_positions=None, linkage_min_count=1, concordance_csv=None, covariation_csv=None,
+               covariation_min_fraction=0.01, covariation_min_count=10,
+               covariation_max_variants=COVARIATION_MAX_VARIANTS):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -1089,6 +1235,12 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     left out (their rows still count in coverage).  A bad set raises
     ValueError before any device work; linkage_positions without linkage_csv
     does nothing.
+    covariation_csv takes, for every pair of the minority variants each run's
+    own counts select (SequenceReport.count_covariation), how often single
+    reads carry one, the other and both; covariation_min_fraction and
+    covariation_min_count select the variants (and min_count the pairs),
+    covariation_max_variants (at most 256) caps them.  A threshold out of
+    range raises ValueError before any device work.
 
     In a sharded job the counting is split: every rank counts the rows in
     its share of aligned.csv and the ranks add their counters up
@@ -1103,8 +1255,14 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     and the tables are added up.  When any rank was given linkage_csv every
     rank counts rank 0's sets over its own rows and the entries are added up
     by (set, haplotype); with variants_csv as well the whole call is
-    unsplit."""
+    unsplit.  When any rank was given covariation_csv the variants are
+    selected from the job's tables (the codon classes are added up for it)
+    with rank 0's thresholds, every rank computes the matrix of its own rows
+    and the matrices are added."""
     global _SHARD
+    covar = _check_covariation(covariation_min_fraction, covariation_min_count, covariation_max_variants)
+    if covariation_csv is None:
+        covar = None
     link = None                 # (sets, min_count) when linkage.csv is asked for
     if linkage_csv is not None:
         if linkage_positions is None:
@@ -1114,7 +1272,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     SHARD_STATS.clear()
     session.stats['aln2counts_source'] = 'csv'
     handles = (nuc_csv, amino_csv, coord_ins_csv, conseq_csv, failed_align_csv, nuc_variants_csv,
-               coverage_summary_csv, variants_csv, nuc_detail_csv, amino_detail_csv, linkage_csv)
+               coverage_summary_csv, variants_csv, nuc_detail_csv, amino_detail_csv, linkage_csv,
+               covariation_csv)
     with session.writer_stage(*handles) as stage:
         split = sh is not None
         if split:
@@ -1129,6 +1288,12 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
             # the sets are rank 0's, so that every rank enters the same collectives
             spec = sh.all_gather_bytes(jsonlib.dumps(link).encode() if link else b'')[0]
             job_link = tuple(jsonlib.loads(spec.decode())) if spec else None
+        job_covar = None
+        if split and not _agree_ok(sh, covariation_csv is None):
+            # rank 0's thresholds, and the job's del counts to select with
+            spec = sh.all_gather_bytes(jsonlib.dumps(covar).encode() if covar else b'')[0]
+            job_covar = tuple(jsonlib.loads(spec.decode())) if spec else None
+            job_detail = job_detail or job_covar is not None
         groups = _load_sharded(sh, aligned_csv) if split else None
         if groups is None:
             if stage.active:
@@ -1137,7 +1302,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
                             nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv,
                             amino_detail_csv=amino_detail_csv, linkage_csv=linkage_csv, link=link,
-                            concordance_csv=concordance_csv)
+                            concordance_csv=concordance_csv, covariation_csv=covariation_csv, covar=covar)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -1148,7 +1313,9 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                         clipping_csv=clipping_csv, nuc_detail_csv=outs[8],
                         conseq_ins_csv=conseq_ins_csv, amino_detail_csv=outs[9], job_detail=job_detail,
                         linkage_csv=None if job_link is None else outs[10] or io.StringIO(), link=job_link,
-                        concordance_csv=concordance_csv)
+                        concordance_csv=concordance_csv,
+                        covariation_csv=None if job_covar is None else outs[11] or io.StringIO(),
+                        covar=job_covar)
         finally:
             _SHARD = None
 
@@ -1212,7 +1379,7 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
                 variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None,
                 amino_detail_csv=None, job_detail=False, linkage_csv=None, link=None,
-                concordance_csv=None):
+                concordance_csv=None, covariation_csv=None, covar=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -1245,6 +1412,9 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
     if linkage_csv is not None:
         report.write_linkage_header(linkage_csv)
         per_run.append(lambda: report.write_linkage(linkage_csv, *link))
+    if covariation_csv is not None:
+        report.write_covariation_header(covariation_csv)
+        per_run.append(lambda: report.write_covariation(covariation_csv, *covar))
     summary = None
     if coverage_summary_csv is not None:
         summary_writer = _csv_writer(coverage_summary_csv, 'coverage')
@@ -1360,6 +1530,15 @@ def _arguments(argv=None):
                      help='input: {coordinate region: [[1-based amino-acid positions], ...]} as JSON')
     cli.add_argument('--linkage_min_count', type=int, default=1, metavar='N',
                      help='leave out linked haplotypes counted fewer than N times (default 1)')
+    cli.add_argument('--covariation_csv', type=argparse.FileType('w'),
+                     help='output: which minority variants single reads carry together, pair by pair')
+    cli.add_argument('--covariation_min_fraction', type=float, default=0.01, metavar='F',
+                     help="a variant is read in at least F of its position's called reads (default 0.01)")
+    cli.add_argument('--covariation_min_count', type=int, default=10, metavar='N',
+                     help='a variant, and the reads called at both positions of a pair, count at least N '
+                          '(default 10)')
+    cli.add_argument('--covariation_max_variants', type=int, default=COVARIATION_MAX_VARIANTS, metavar='N',
+                     help='keep the N most counted variants of a run (default and most: 256)')
     return cli.parse_args(argv)
 
 
@@ -1373,7 +1552,10 @@ def main():
                clipping_csv=a.clipping_csv, nuc_detail_csv=a.nuc_detail_csv,
                conseq_ins_csv=a.conseq_ins_csv, amino_detail_csv=a.amino_detail_csv,
                linkage_csv=a.linkage_csv, linkage_positions=a.linkage_positions,
-               linkage_min_count=a.linkage_min_count, concordance_csv=a.concordance_csv)
+               linkage_min_count=a.linkage_min_count, concordance_csv=a.concordance_csv,
+               covariation_csv=a.covariation_csv, covariation_min_fraction=a.covariation_min_fraction,
+               covariation_min_count=a.covariation_min_count,
+               covariation_max_variants=a.covariation_max_variants)
 
 
 if __name__ == '__main__':
