@@ -581,6 +581,31 @@ int mh_sam2aln_concordance_write(mh_ctx *ctx, int which, int fd, int64_t offset,
  * Arrays NULL: only *n and *read_n. */
 int mh_sam2aln_conc_counts(mh_ctx *ctx, int32_t *name_id, int64_t *pos, int32_t *counts5, int64_t cap,
                            int64_t *n, int64_t *reads5, int64_t read_cap, int64_t *read_n);
+/* Strand support of the last sam2aln call on this context: strand.csv
+ * (refname,qcut,pos,A_fwd,A_rev,A_both,C_fwd,...,del_fwd,del_rev,del_both).
+ * A unit counts at the q-cutoffs at which it gives aligned.csv a sequence.
+ * At index j of its merged string (position j + 1) with merged character m in
+ * "ACGT-", a mate supports m when its own expansion (apply_cigar at POS)
+ * holds the byte m there, whatever its quality; the unit adds 1 to m_fwd when
+ * a supporting mate has FLAG 0x10 clear, 1 to m_rev when one has it set, 1 to
+ * m_both when both hold.  So m_fwd + m_rev - m_both is the count of the
+ * aligned.csv rows that hold m there.  Rows with any count, names sorted as
+ * strings, then the call's cutoffs in its order, then positions; '\n' line
+ * ends.  Nothing is computed before the first of these three calls asks: the
+ * pass (k_s2a_strand, k_s2a_strand_scan) then runs once over the rows, units
+ * and merge results the call left on the device, so ask before the next
+ * sam2aln or mapping call.  buf NULL: only *used = bytes needed.  -3 with a
+ * message naming the reference when its rows span more than 2^26 positions,
+ * and when the counters of all references and cutoffs would exceed 2^30
+ * bytes; the call's other outputs stay available. */
+int mh_sam2aln_strand(mh_ctx *ctx, char *buf, size_t cap, size_t *used);
+/* The same text written to fd at offset with pwrite; *written = its size. */
+int mh_sam2aln_strand_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written);
+/* The same counts as arrays in the text's row order: name_id (as in
+ * mh_sam2aln_clip_counts), the cutoff, pos and fifteen counts per row in the
+ * columns' order; *n = rows.  Arrays NULL: only *n. */
+int mh_sam2aln_strand_counts(mh_ctx *ctx, int32_t *name_id, int32_t *qcut, int64_t *pos,
+                             int32_t *counts15, int64_t cap, int64_t *n);
 /* conseq_ins.csv of the last sam2aln call on this context: the insertions
  * that remap's last pass left out of the consensus, merged per unit as the
  * reference's merge_inserts merges them and counted per distinct string

@@ -98,6 +98,26 @@ struct S2AConc {
     unsigned long long *d_rd = nullptr;                      // the per-read sums (64-bit)
 };
 
+// strand support of the last call (mh_sam2aln_strand), counted on the first
+// request from the same rows, units and merge results: per (reference,
+// q-cutoff, position) and merged character (A, C, G, T, '-') the units with a
+// supporting mate on the forward strand, on the reverse strand, and on both
+constexpr int STRAND_KEYS = 15;                              // character * 3 + (0 fwd only, 1 rev only, 2 both)
+constexpr int64_t S2A_STRAND_MAX_BYTES = (int64_t)1 << 30;   // the class planes in HBM at most
+
+struct S2AStrand {
+    bool done = false;
+    std::vector<int32_t> name, qcut;    // per row, by (name as Python sorts str, the call's cutoff order,
+    std::vector<int64_t> pos;           //   pos): index into S2AState::names, the cutoff, 1-based position
+    std::vector<int32_t> count;         // STRAND_KEYS per row: A_fwd, A_rev, A_both, C_fwd, ... del_both
+    std::string text;                   // strand.csv, formatted on first use
+    bool text_valid = false;
+    int64_t *d_lo = nullptr, *d_base = nullptr;              // per reference: window start, offset in a plane
+    int32_t *d_wlen = nullptr, *d_acc = nullptr, *d_idx = nullptr, *d_cnt = nullptr,
+            *d_n = nullptr;                                  // d_n: rows per (cutoff, reference), then the error flag
+    uint8_t *d_orient = nullptr;                             // per merge unit: bit 0 row1 reversed, bit 1 row2
+};
+
 // merged insertions of the last call (mh_sam2aln_conseq_ins), counted on the
 // first request from the same rows and units.  One record per (listed unit,
 // consensus key); one entry per (record, q-cutoff): entry = record * n_cut + k
@@ -191,6 +211,7 @@ struct S2AState {
     S2AClip clip;
     S2AIns ins;
     S2AConc conc;
+    S2AStrand strand;
     // shape of the last k_s2a_merge launch, kept for mh_test_sam2aln_info
     // (host bookkeeping; nothing reads it otherwise).  wpb and blocks stay 0
     // when the call was refused before the launch
@@ -227,6 +248,7 @@ inline void s2a_begin(Ctx &c, S2AState &S)
     S.clip.text_valid = false;
     S.ins.done = S.ins.text_valid = false;
     S.conc.done = S.conc.text_valid[0] = S.conc.text_valid[1] = false;
+    S.strand.done = S.strand.text_valid = false;
     for (auto &o : S.out_cache) std::vector<std::string>().swap(o);
     S.out_valid = 0;
 }
@@ -256,6 +278,9 @@ int s2a_ins_run(Ctx &c, S2AState &S);
 // k_s2a_conc and k_s2a_conc_scan over the paired units of the last s2a_run,
 // once per call: S.conc's position rows and read table
 int s2a_conc_run(Ctx &c, S2AState &S);
+// k_s2a_strand and k_s2a_strand_scan over the units of the last s2a_run whose
+// merge entries are S2A_OK, once per call: S.strand's rows
+int s2a_strand_run(Ctx &c, S2AState &S);
 // Units, failure causes, group names and QNAMEs of the resident rows (one
 // per read, in read order) instead of s2a_parse: S.pos, S.flag, S.n_cig,
 // S.cig_off and S.cig hold the rows as k_s2a_stage wrote them; sam_ref[r]

@@ -35,6 +35,9 @@
 //                 disagree, per consensus position and per read cycle and
 //                 quality (concordance.csv, cycle_concordance.csv; no
 //                 reference code)
+//   k_s2a_strand, k_s2a_strand_scan   only when mh_sam2aln_strand asks: per
+//                 position and merged base the units whose supporting mate is
+//                 forward, reversed or both (strand.csv; no reference code)
 // Bit-for-bit specification: the reference itself (tests/golden/e2e/*/aligned.csv
 // etc. were produced by running micall.core.sam2aln on the same remap.csv).
 #include <fcntl.h>
@@ -98,6 +101,13 @@ static void s2a_free_device(S2AState &S)
     Q.d_orient = nullptr;
     Q.d_rd = nullptr;
     Q.done = false;
+    S2AStrand &T = S.strand;
+    hipFree(T.d_lo); hipFree(T.d_base); hipFree(T.d_wlen); hipFree(T.d_acc); hipFree(T.d_idx);
+    hipFree(T.d_cnt); hipFree(T.d_n); hipFree(T.d_orient);
+    T.d_lo = T.d_base = nullptr;
+    T.d_wlen = T.d_acc = T.d_idx = T.d_cnt = T.d_n = nullptr;
+    T.d_orient = nullptr;
+    T.done = false;
     S.dcap.clear();
 }
 
@@ -1653,6 +1663,557 @@ static int s2a_conc_of(mh_ctx *ctx, const char *what, int which, S2AState **out)
 }
 
 // ---------------------------------------------------------------------------
+// Strand support (strand.csv; DESIGN.md section 6, "Strand support").  A unit
+// counts at the cutoffs at which its merge entry is S2A_OK.  At index j of its
+// merged string (position y = j + 1) with merged character m in "ACGT-", a
+// mate supports m when its own expansion holds the byte m at y; the unit adds
+// 1 to m_fwd / m_rev when a supporting mate is forward / reversed and to
+// m_both when both hold.
+//
+// k_s2a_strand       one wave per unit, the mates expanded into LDS as
+//                    k_s2a_merge expands them, (ch, thr) of every position from
+//                    the merge's own s2a_pos.  With the cutoffs sorted, a
+//                    position passes the first p of them and the unit is OK at
+//                    a set of them (from res, not assumed monotone): when that
+//                    set is the first nok cutoffs, the position makes ONE add,
+//                    to class min(p, nok) of key = character * 3 + (fwd only,
+//                    rev only, both); the count at sorted cutoff k is the sum of
+//                    the classes above k.  Any other OK set adds +1 / -1 at the
+//                    ends of its runs, straight to HBM.  The one add goes to the
+//                    block's LDS window: STRAND_KEYS * classes planes of `win`
+//                    positions from the address win0 of the call's densest
+//                    stretch, 16-bit counters two to a word, laid out so that a
+//                    wave's 64 consecutive positions fall into 64 different
+//                    words and banks.  A unit adds at most 1 to a counter and
+//                    the host sizes the grid so that a block takes fewer than
+//                    65536 units: no half carries into the other.  Adds outside
+//                    the window go straight to HBM.  The block flushes one
+//                    atomic per used counter.  Integer adds only.
+// k_s2a_strand_scan  one block per (reference, cutoff): the classes above the
+//                    cutoff summed per key, fwd = fwd only + both, rev = rev
+//                    only + both, and the positions with any count compacted in
+//                    position order as k_s2a_clip_scan compacts them.
+// ---------------------------------------------------------------------------
+constexpr int STRAND_WPB = 16;
+constexpr int STRAND_UNITS_PER_WAVE = 32;     // a block's flush is shared by 512 units at least
+constexpr int64_t STRAND_BLOCK_CAP = 256;     // one block a CU: each flushes up to a window of atomics
+constexpr int64_t STRAND_BLOCK_UNITS = 65535; // units of one block at most: what a 16-bit counter holds
+
+struct StrandArgs {
+    const uint8_t *seq, *qual;
+    const int64_t *soff;
+    const int32_t *pos, *cig_off, *n_cig;
+    const uint32_t *cig;
+    const int64_t *units;     // per merge unit: row1, row2 (-1: single)
+    const int32_t *uref;
+    const uint8_t *orient;    // per merge unit: bit 0 row1 is reversed, bit 1 row2
+    const int32_t *res;       // the merge's 4 per entry: status first
+    int64_t n;
+    int n_cut;
+    unsigned char cut[S2A_MAX_CUTS];    // q_cutoff + 33, ascending
+    unsigned char entry[S2A_MAX_CUTS];  // the call's index of sorted cutoff k
+    int span_cap, ops_cap, wave_bytes;
+    const int64_t *lo, *base; // per reference: first padded index of its window, its offset in a plane
+    const int32_t *wlen;      // per reference: indexes in its window
+    int64_t total;            // entries of one plane
+    int64_t win0;             // first address of the LDS window
+    int win;                  // its positions, a multiple of 128
+    int32_t *acc;             // n_cut * STRAND_KEYS planes: (class - 1) * STRAND_KEYS + key
+    int32_t *err;             // set when a position falls outside its window
+};
+
+__global__ __launch_bounds__(64 * STRAND_WPB) void k_s2a_strand(StrandArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wpb = blockDim.x >> 6;
+    const int half = A.win >> 1;                                // words of one plane
+    const int nword = A.n_cut * STRAND_KEYS * half;
+    uint32_t *cnt = (uint32_t *)smem;
+    unsigned char *wb = smem + (size_t)nword * 4 + (size_t)wv * A.wave_bytes;
+    char *cq = (char *)wb;                                     // c0 q0 c1 q1, span_cap each
+    int32_t *opref = (int32_t *)(wb + 4 * (size_t)A.span_cap); // ops_cap + 1 per mate
+    int32_t *opread = opref + 2 * (A.ops_cap + 1);
+    for (int s = threadIdx.x; s < nword; s += blockDim.x) cnt[s] = 0u;
+    __syncthreads();
+
+    for (int64_t u = (int64_t)blockIdx.x * wpb + wv; u < A.n; u += (int64_t)gridDim.x * wpb) {
+        // the cutoffs (sorted) at which the unit is OK
+        int en = 0;                                // lane k < n_cut: the entry of sorted cutoff k
+#pragma unroll
+        for (int k = 0; k < S2A_MAX_CUTS; ++k) en = lane == k ? A.entry[k] : en;
+        const bool isok = lane < A.n_cut && A.res[4 * (u * A.n_cut + en)] == S2A_OK;
+        const unsigned okm = (unsigned)__ballot(isok);
+        if (!okm) continue;
+        const int nok = __popc(okm);
+        const bool prefix = okm == (1u << nok) - 1u;
+        const int64_t rows[2] = {A.units[2 * u], A.units[2 * u + 1]};
+        const int nm = rows[1] >= 0 ? 2 : 1;
+        // named mates, every loop over them unrolled (see k_s2a_merge)
+        Mate mt[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            mt[k].row = -1; mt[k].pad = 0; mt[k].rf = 0; mt[k].len = 0;
+            mt[k].c = cq + 2 * k * A.span_cap;
+            mt[k].q = cq + (2 * k + 1) * A.span_cap;
+        }
+        // ---- apply_cigar as k_s2a_merge runs it ----
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (k >= nm) break;
+            const int64_t r = rows[k];
+            const int nc = A.n_cig[r];
+            const uint32_t *ops = A.cig + A.cig_off[r];
+            int32_t *oref = opref + k * (A.ops_cap + 1), *ord = opread + k * (A.ops_cap + 1);
+            int rf0 = 0, rd0 = 0;
+            for (int o0 = 0; o0 < nc; o0 += 64) {
+                const int o = o0 + lane;
+                int dref = 0, dread = 0, isd = 0;
+                if (o < nc) {
+                    const uint32_t op = ops[o];
+                    const int n = (int)(op >> 4), t = (int)(op & 15);
+                    if (t == MH_OP_M) { dref = n; dread = n; }
+                    else if (t == MH_OP_D) { dref = n; isd = 1; }
+                    else dread = n;                      // I, S (checked on the host)
+                }
+                const int iref = s2a_scan(dref, lane), iread = s2a_scan(dread, lane);
+                if (o < nc) {
+                    oref[o] = rf0 + iref - dref;
+                    ord[o] = isd ? -1 : rd0 + iread - dread;
+                }
+                rf0 += __shfl(iref, 63, 64);
+                rd0 += __shfl(iread, 63, 64);
+            }
+            if (lane == 0) { oref[nc] = rf0; ord[nc] = rd0; }
+            const int p = A.pos[r] - 1;
+            mt[k].row = (int)r;
+            mt[k].pad = p > 0 ? p : 0;
+            mt[k].rf = rf0;
+            mt[k].len = mt[k].pad + rf0;
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (k >= nm) break;
+            const int64_t r = rows[k];
+            const int32_t *oref = opref + k * (A.ops_cap + 1), *ord = opread + k * (A.ops_cap + 1);
+            const uint8_t *s = A.seq + A.soff[r], *q = A.qual + A.soff[r];
+            for (int t = lane; t < mt[k].rf; t += 64) {
+                int o = 0;
+                while (oref[o + 1] <= t) ++o;
+                const int rd = ord[o];
+                char c = '-', qq = ' ';
+                if (rd >= 0) {
+                    const int x = rd + (t - oref[o]);
+                    c = (char)s[x];
+                    qq = (char)q[x];
+                }
+                mt[k].c[t] = c;
+                mt[k].q[t] = qq;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+        // ---- merge_pairs roles and starts, as k_s2a_merge takes them ----
+        const bool single = nm == 1;
+        const int ob = A.orient[u];
+        Mate a = mt[0], b = mt[0];
+        bool reva = ob & 1, revb = ob & 1;
+        if (!single) {
+            if (mt[0].len > mt[1].len) { a = mt[1]; b = mt[0]; reva = ob & 2; }
+            else { a = mt[0]; b = mt[1]; revb = ob & 2; }
+        }
+        const int len2 = b.len;
+        int rev_start = 1 << 30, fwd_start = 1 << 30;
+        if (!single) {
+            for (int i0 = 0; i0 < len2; i0 += 64) {
+                const int i = i0 + lane;
+                int rs = 1 << 30, fs = 1 << 30;
+                if (i < len2) {
+                    const char c2 = (i >= b.pad) ? b.c[i - b.pad] : '-';
+                    if (c2 != '-') rs = i;
+                    if (i < a.len) {
+                        const char c1 = (i >= a.pad) ? a.c[i - a.pad] : '-';
+                        if (!(c1 == '-' && c2 == '-')) fs = i;
+                    }
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    rs = min(rs, __shfl_xor(rs, o, 64));
+                    fs = min(fs, __shfl_xor(fs, o, 64));
+                }
+                rev_start = min(rev_start, rs);
+                fwd_start = min(fwd_start, fs);
+                if (rev_start < (1 << 30) && (fwd_start < (1 << 30) || i0 + 64 >= a.len)) break;
+            }
+        }
+        const bool fwd = single || fwd_start < a.len;
+        const int ibase = fwd ? 0 : a.len;
+        const int mlen = len2 - ibase;
+        const int ref = A.uref[u];
+        const int64_t w0 = A.lo[ref], gb = A.base[ref];
+        const int wl = A.wlen[ref];
+        // no mate holds a byte below the smaller pad: nothing supports there
+        const int jlo = (single ? b.pad : min(a.pad, b.pad)) & ~63;
+        for (int j0 = jlo; j0 < mlen; j0 += 64) {
+            const int j = j0 + lane;
+            if (j >= mlen) continue;
+            const int i = j + ibase;
+            char ch = '-';
+            unsigned char thr = S2A_ALWAYS;
+            if (single || !fwd || i >= fwd_start) s2a_pos(i, a, b, single, rev_start, ch, thr);
+            const int mi = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : ch == '-' ? 4 : -1;
+            if (mi < 0) continue;
+            // support is looked up at y = j + 1, padded index j, whatever ibase
+            const bool sa = !single && j >= a.pad && j < a.len && a.c[j - a.pad] == ch;
+            const bool sb = j >= b.pad && j < b.len && b.c[j - b.pad] == ch;
+            const bool sf = (sa && !reva) || (sb && !revb), sr = (sa && reva) || (sb && revb);
+            if (!sf && !sr) continue;
+            const int key = mi * 3 + (sf && sr ? 2 : sr ? 1 : 0);
+            int p = 0;
+#pragma unroll
+            for (int k = 0; k < S2A_MAX_CUTS; ++k) p += k < A.n_cut && thr > A.cut[k];
+            const int64_t rel = (int64_t)j - w0;
+            if (rel < 0 || rel > (int64_t)wl) {          // the host sized the window from the same rows
+                atomicExch(A.err, 1);
+                continue;
+            }
+            const int64_t g = gb + rel;
+            if (prefix) {
+                const int cls = min(p, nok);
+                if (cls < 1) continue;
+                const int plane = (cls - 1) * STRAND_KEYS + key;
+                const int64_t x = g - A.win0;
+                if (x >= 0 && x < (int64_t)A.win) {
+                    const int xi = (int)x;
+                    atomicAdd(&cnt[plane * half + ((xi >> 7) << 6) + (xi & 63)], 1u << (((xi >> 6) & 1) << 4));
+                } else {
+                    atomicAdd(&A.acc[(int64_t)plane * A.total + g], 1);
+                }
+            } else {
+                // runs of counted cutoffs [s, e): +1 to class e, -1 to class s
+#pragma unroll
+                for (int k = 0; k < S2A_MAX_CUTS; ++k) {
+                    const bool in = k < p && ((okm >> k) & 1u);
+                    const bool before = k > 0 && k - 1 < p && ((okm >> (k - 1)) & 1u);
+                    const bool after = k + 1 < p && ((okm >> (k + 1)) & 1u);
+                    if (in && !after) atomicAdd(&A.acc[(int64_t)(k * STRAND_KEYS + key) * A.total + g], 1);
+                    if (in && !before && k > 0)
+                        atomicAdd(&A.acc[(int64_t)((k - 1) * STRAND_KEYS + key) * A.total + g], -1);
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();              // the next unit rewrites the expansion
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < nword; s += blockDim.x) {
+        const uint32_t v = cnt[s];
+        if (!v) continue;
+        const int plane = s / half, r = s - plane * half;
+        const int64_t g = A.win0 + ((int64_t)(r >> 6) << 7) + (r & 63);
+        int32_t *dst = A.acc + (int64_t)plane * A.total;
+        if (v & 0xffffu) atomicAdd(&dst[g], (int32_t)(v & 0xffffu));      // g + 64 < total where the high half counted
+        if (v >> 16) atomicAdd(&dst[g + 64], (int32_t)(v >> 16));
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_s2a_strand_scan(const int64_t *base, const int32_t *wlen,
+                                                          int64_t total, int n_cut, int nref,
+                                                          const int32_t *acc, int32_t *idx_out,
+                                                          int32_t *cnt_out, int32_t *n_out,
+                                                          const unsigned char *rank_of)
+{
+    __shared__ int32_t wnz[16];
+    const int ref = blockIdx.x, kk = blockIdx.y;   // kk: the call's cutoff index
+    const int k0 = rank_of[kk];                    // classes k0 + 1 .. n_cut pass it
+    const int64_t b = base[ref];
+    const int n = wlen[ref] + 1;           // 0 for a reference without units (wlen -1)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int64_t ob = (int64_t)kk * STRAND_KEYS * total;
+    int outn = 0;
+    for (int i0 = 0; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + (int)threadIdx.x;
+        int32_t v[STRAND_KEYS];
+        int any = 0;
+#pragma unroll
+        for (int key = 0; key < STRAND_KEYS; ++key) {
+            int s = 0;
+            if (i < n)
+                for (int cl = k0; cl < n_cut; ++cl) s += acc[(int64_t)(cl * STRAND_KEYS + key) * total + b + i];
+            v[key] = s;
+            any |= s;
+        }
+        const int nz = any != 0;
+        const int f = s2a_scan(nz, lane);
+        if (lane == 63) wnz[wv] = f;
+        __syncthreads();
+        int pre = 0, tot = 0;
+        for (int w = 0; w < nw; ++w) { const int t = wnz[w]; pre += w < wv ? t : 0; tot += t; }
+        if (nz) {
+            const int64_t k = b + outn + pre + f - 1;      // < b + n: one row per position at most
+            idx_out[(int64_t)kk * total + k] = i;
+#pragma unroll
+            for (int m = 0; m < 5; ++m) {
+                const int both = v[3 * m + 2];
+                cnt_out[ob + (int64_t)(3 * m) * total + k] = v[3 * m] + both;
+                cnt_out[ob + (int64_t)(3 * m + 1) * total + k] = v[3 * m + 1] + both;
+                cnt_out[ob + (int64_t)(3 * m + 2) * total + k] = both;
+            }
+        }
+        outn += tot;
+        __syncthreads();                   // wnz is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) n_out[kk * nref + ref] = outn;
+}
+
+int s2a_strand_run(Ctx &c, S2AState &S)
+{
+    S2AStrand &T = S.strand;
+    if (T.done) return 0;
+    if (S.clip.state == CLIP_NONE) {
+        set_error("sam2aln strand: no rows of a sam2aln call are on the device");
+        return -3;
+    }
+    const S2ADevRows &rows = S.clip.rows;
+    if (S.n_merge && rows.cig != S.d_cig && (!c.map.valid || rows.cig != c.map.pool)) {
+        set_error("sam2aln strand: the mapping pass the rows came from is gone");
+        return -3;
+    }
+    if (S.n_merge && rows.soff != S.d_soff && (rows.soff != c.reads.off || S.staged_reads != c.reads.n)) {
+        set_error("sam2aln strand: the resident reads the rows came from are gone");
+        return -3;
+    }
+    T.name.clear(); T.qcut.clear(); T.pos.clear(); T.count.clear();
+    T.text_valid = false;
+    const int nref = (int)S.names.size();
+    const int nc = (int)S.q_cutoffs.size();
+    const int64_t nu = (int64_t)S.u1.size();
+    if (S.n_merge == 0 || nref == 0) { T.done = true; return 0; }
+    // ---- per unit its strand bits; each reference's window of padded indexes
+    // from its units' rows; the adds per 64 addresses, for the LDS window ----
+    std::vector<uint8_t> orient((size_t)S.n_merge, 0);
+    std::vector<int64_t> lo((size_t)nref, INT64_MAX), hi((size_t)nref, INT64_MIN);
+    std::vector<int64_t> ulo((size_t)S.n_merge, 0), uhi((size_t)S.n_merge, 0);
+    for (int64_t u = 0; u < nu; ++u) {
+        if (S.ucause[u] >= 0) continue;
+        const int g = S.name_id[u];
+        const int64_t m = S.merge_of_unit[u];
+        int bits = 0, k = 0;
+        int64_t l = INT64_MAX, h = 0;
+        for (int64_t r : {S.u1[u], S.upaired[u] ? S.u2[u] : (int64_t)-1}) {
+            if (r < 0) continue;
+            int64_t span = 0;
+            for (int o = 0; o < S.n_cig[r]; ++o) {
+                const uint32_t op = S.cig[S.cig_off[r] + o];
+                if ((op & 15) == MH_OP_M || (op & 15) == MH_OP_D) span += op >> 4;
+            }
+            const int64_t pad = S.pos[r] - 1 > 0 ? S.pos[r] - 1 : 0;
+            l = std::min(l, pad);
+            h = std::max(h, pad + span);
+            bits |= ((S.flag[r] & 0x10) ? 1 : 0) << k++;
+        }
+        orient[(size_t)m] = (uint8_t)bits;
+        ulo[(size_t)m] = l;
+        uhi[(size_t)m] = h;
+        lo[g] = std::min(lo[g], l);
+        hi[g] = std::max(hi[g], h);
+    }
+    std::vector<int64_t> base((size_t)nref + 1, 0);
+    std::vector<int32_t> wlen((size_t)nref, -1);
+    for (int g = 0; g < nref; ++g) {
+        if (lo[g] > hi[g]) { lo[g] = 0; base[g + 1] = base[g]; continue; }
+        if (hi[g] - lo[g] > S2A_CLIP_MAX_WINDOW) {
+            set_error("sam2aln strand: the rows of %s span positions %lld to %lld, more than %lld",
+                      S.names[g].c_str(), (long long)lo[g] + 1, (long long)hi[g],
+                      (long long)S2A_CLIP_MAX_WINDOW);
+            return -3;
+        }
+        wlen[g] = (int32_t)(hi[g] - lo[g]);
+        base[g + 1] = base[g] + wlen[g] + 1;
+    }
+    // a plane is padded to whole 128-address groups: the flush's high halves stay inside it
+    const int64_t total = (base[nref] + 127) & ~(int64_t)127;
+    const int64_t planes = (int64_t)nc * STRAND_KEYS;
+    // acc, and idx + cnt of the compaction, int32 each
+    if ((2 * planes + nc) * total * (int64_t)sizeof(int32_t) > S2A_STRAND_MAX_BYTES) {
+        set_error("sam2aln strand: %lld positions at %d q-cutoffs need more than %lld bytes of counters",
+                  (long long)base[nref], nc, (long long)S2A_STRAND_MAX_BYTES);
+        return -3;
+    }
+    // ---- the launch: the waves' expansions as the merge sized them, the rest
+    // of the block's LDS for the window ----
+    const int span_cap = S.info.span_cap, ops_cap = S.info.ops_cap, wave_bytes = S.info.wave_bytes;
+    int wpb = STRAND_WPB;
+    while (wpb > 1 && (size_t)wpb * wave_bytes + 128 * 2 * (size_t)planes > S2A_LDS_BYTES) --wpb;
+    if ((size_t)wpb * wave_bytes + 128 * 2 * (size_t)planes > S2A_LDS_BYTES) {
+        set_error("sam2aln strand: reference span %d too long for LDS", span_cap);
+        return -3;
+    }
+    int64_t win = (int64_t)((S2A_LDS_BYTES - (size_t)wpb * wave_bytes) / (2 * (size_t)planes)) & ~(int64_t)127;
+    if (win > total) win = total;
+    // the window starts where a stretch of `win` addresses takes the most adds
+    int64_t win0 = 0;
+    if (win < total) {
+        const int64_t nb = total >> 7, wb = win >> 7;
+        std::vector<int64_t> mass((size_t)nb + 1, 0);
+        for (int64_t u = 0; u < nu; ++u) {
+            if (S.ucause[u] >= 0) continue;
+            const int64_t m = S.merge_of_unit[u];
+            const int g = S.name_id[u];
+            const int64_t mid = base[g] + (ulo[(size_t)m] + uhi[(size_t)m]) / 2 - lo[g];
+            mass[(size_t)(mid >> 7)] += uhi[(size_t)m] - ulo[(size_t)m];
+        }
+        int64_t run = 0, best = -1;
+        for (int64_t x = 0; x < nb; ++x) {
+            run += mass[(size_t)x];
+            if (x >= wb) run -= mass[(size_t)(x - wb)];
+            if (x >= wb - 1 && run > best) { best = run; win0 = (x - wb + 1) << 7; }
+        }
+    }
+    hipStream_t s = c.stream;
+    std::vector<unsigned char> order((size_t)nc), rank_of((size_t)nc);
+    for (int k = 0; k < nc; ++k) order[k] = (unsigned char)k;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return S.q_cutoffs[x] < S.q_cutoffs[y]; });
+    for (int k = 0; k < nc; ++k) rank_of[order[k]] = (unsigned char)k;
+    if (int st = s2a_upload(S, T.d_orient, orient, s)) return st;
+    if (int st = s2a_upload(S, T.d_lo, lo, s)) return st;
+    if (int st = s2a_upload(S, T.d_base, base, s)) return st;
+    if (int st = s2a_upload(S, T.d_wlen, wlen, s)) return st;
+    if (int st = dev_reserve(S, T.d_acc, sizeof(int32_t) * (size_t)(planes * total))) return st;
+    if (int st = dev_reserve(S, T.d_idx, sizeof(int32_t) * (size_t)(nc * total))) return st;
+    if (int st = dev_reserve(S, T.d_cnt, sizeof(int32_t) * (size_t)(planes * total))) return st;
+    // rows per (cutoff, reference), the error flag, then the cutoffs' ranks as bytes
+    const size_t n_words = (size_t)nc * nref + 1;
+    if (int st = dev_reserve(S, T.d_n, sizeof(int32_t) * (n_words + 2))) return st;
+    MH_HIP(hipMemsetAsync(T.d_acc, 0, sizeof(int32_t) * (size_t)(planes * total), s));
+    MH_HIP(hipMemsetAsync(T.d_n, 0, sizeof(int32_t) * n_words, s));
+    unsigned char *d_rank = (unsigned char *)(T.d_n + n_words);
+    MH_HIP(hipMemcpyAsync(d_rank, rank_of.data(), (size_t)nc, hipMemcpyHostToDevice, s));
+    StrandArgs a{rows.seq, rows.qual, rows.soff, rows.pos, rows.cig_off, rows.n_cig, rows.cig,
+                 S.d_units, S.d_uref, T.d_orient, S.d_res, S.n_merge, nc, {}, {}, span_cap, ops_cap,
+                 wave_bytes, T.d_lo, T.d_base, T.d_wlen, total, win0, (int)win, T.d_acc,
+                 T.d_n + (n_words - 1)};
+    for (int k = 0; k < nc; ++k) {
+        a.cut[k] = (unsigned char)(S.q_cutoffs[order[k]] + 33);
+        a.entry[k] = order[k];
+    }
+    int64_t blocks = (S.n_merge + wpb * STRAND_UNITS_PER_WAVE - 1) / (wpb * STRAND_UNITS_PER_WAVE);
+    if (blocks > STRAND_BLOCK_CAP) blocks = STRAND_BLOCK_CAP;
+    const int64_t max_blocks = c.test_caps.s2a_max_blocks;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    // a 16-bit counter of a block cannot wrap: a unit adds at most 1 to it, and a
+    // block of `blocks` takes at most ceil(ceil(n / wpb) / blocks) * wpb units
+    while (((S.n_merge + wpb - 1) / wpb + blocks - 1) / blocks * wpb > STRAND_BLOCK_UNITS) ++blocks;
+    const size_t dyn = (size_t)planes * (size_t)win * 2 + (size_t)wpb * wave_bytes;
+    MH_HIP(hipFuncSetAttribute((const void *)k_s2a_strand, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)dyn));
+    const int p0 = prof_begin(c, "k_s2a_strand");
+    hipLaunchKernelGGL(k_s2a_strand, dim3((unsigned)blocks), dim3(64 * wpb), dyn, s, a);
+    prof_end(c, p0);
+    MH_HIP(hipGetLastError());
+    const int p1 = prof_begin(c, "k_s2a_strand_scan");
+    hipLaunchKernelGGL(k_s2a_strand_scan, dim3((unsigned)nref, (unsigned)nc), dim3(1024), 0, s, T.d_base,
+                       T.d_wlen, total, nc, nref, T.d_acc, T.d_idx, T.d_cnt, T.d_n, d_rank);
+    prof_end(c, p1);
+    MH_HIP(hipGetLastError());
+    std::vector<int32_t> n_out(n_words);
+    MH_HIP(hipMemcpyAsync(n_out.data(), T.d_n, sizeof(int32_t) * n_words, hipMemcpyDeviceToHost, s));
+    MH_HIP(hipStreamSynchronize(s));
+    prof_flush(c);
+    if (n_out[n_words - 1]) {
+        set_error("sam2aln strand: a position fell outside its reference's window");
+        return -4;
+    }
+    // ---- rows: references as Python sorts str, the call's cutoffs, positions ----
+    std::vector<int> names((size_t)nref);
+    for (int g = 0; g < nref; ++g) names[g] = g;
+    std::sort(names.begin(), names.end(), [&](int x, int y) { return S.names[x] < S.names[y]; });
+    std::vector<int64_t> at((size_t)nref * nc + 1, 0);
+    for (int k = 0; k < nref; ++k)
+        for (int kk = 0; kk < nc; ++kk) {
+            const int g = names[k], n = n_out[(size_t)kk * nref + g];
+            if (n < 0 || n > wlen[g] + 1) {
+                set_error("sam2aln strand: %d positions counted in a window of %d", n, wlen[g] + 1);
+                return -4;
+            }
+            at[(size_t)k * nc + kk + 1] = at[(size_t)k * nc + kk] + n;
+        }
+    const size_t nrow = (size_t)at[(size_t)nref * nc];
+    std::vector<int32_t> idx(nrow), cnt(STRAND_KEYS * nrow);
+    for (int k = 0; k < nref; ++k)
+        for (int kk = 0; kk < nc; ++kk) {
+            const int g = names[k], n = n_out[(size_t)kk * nref + g];
+            if (!n) continue;
+            const int64_t first = at[(size_t)k * nc + kk];
+            const size_t nb = sizeof(int32_t) * (size_t)n;
+            MH_HIP(hipMemcpyAsync(idx.data() + first, T.d_idx + (int64_t)kk * total + base[g], nb,
+                                  hipMemcpyDeviceToHost, s));
+            for (int key = 0; key < STRAND_KEYS; ++key)
+                MH_HIP(hipMemcpyAsync(cnt.data() + key * nrow + first,
+                                      T.d_cnt + ((int64_t)kk * STRAND_KEYS + key) * total + base[g], nb,
+                                      hipMemcpyDeviceToHost, s));
+        }
+    MH_HIP(hipStreamSynchronize(s));
+    T.name.resize(nrow);
+    T.qcut.resize(nrow);
+    T.pos.resize(nrow);
+    T.count.resize(STRAND_KEYS * nrow);
+    for (int k = 0; k < nref; ++k)
+        for (int kk = 0; kk < nc; ++kk)
+            for (int64_t j = at[(size_t)k * nc + kk]; j < at[(size_t)k * nc + kk + 1]; ++j) {
+                T.name[j] = names[k];
+                T.qcut[j] = S.q_cutoffs[kk];
+                T.pos[j] = lo[names[k]] + idx[j] + 1;
+                for (int key = 0; key < STRAND_KEYS; ++key) T.count[STRAND_KEYS * j + key] = cnt[key * nrow + j];
+            }
+    T.done = true;
+    return 0;
+}
+
+// strand.csv of S.strand's rows
+static void s2a_strand_text(S2AState &S)
+{
+    S2AStrand &T = S.strand;
+    if (T.text_valid) return;
+    std::string &o = T.text;
+    o.assign("refname,qcut,pos,A_fwd,A_rev,A_both,C_fwd,C_rev,C_both,G_fwd,G_rev,G_both,"
+             "T_fwd,T_rev,T_both,del_fwd,del_rev,del_both\n");
+    for (size_t j = 0; j < T.name.size(); ++j) {
+        const std::string &rn = S.names[T.name[j]];
+        csv_field(o, rn.data(), rn.size());
+        o.push_back(',');
+        o += std::to_string(T.qcut[j]);
+        o.push_back(',');
+        o += std::to_string((long long)T.pos[j]);
+        for (int key = 0; key < STRAND_KEYS; ++key) {
+            o.push_back(',');
+            o += std::to_string(T.count[STRAND_KEYS * j + key]);
+        }
+        o.push_back('\n');
+    }
+    T.text_valid = true;
+}
+
+// the strand support of the context's last sam2aln call, counted now if not yet
+static int s2a_strand_of(mh_ctx *ctx, const char *what, bool text, S2AState **out)
+{
+    Ctx &c = *ctx_of(ctx);
+    if (!c.s2a) { set_error("%s: no sam2aln results", what); return -3; }
+    MH_HIP(hipSetDevice(c.device));
+    try {
+        if (int st = s2a_strand_run(c, *c.s2a)) return st;
+        if (text) s2a_strand_text(*c.s2a);
+    } catch (const std::exception &e) {
+        c.s2a->strand.done = c.s2a->strand.text_valid = false;
+        set_error("%s: out of memory (%s)", what, e.what());
+        return -2;
+    }
+    *out = c.s2a;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Merged insertions (conseq_ins.csv; DESIGN.md section 6, "Merged
 // insertions").  Per read, walking the CIGAR with ref = POS - 1 and left = 0:
 // an I op of n > 0 bytes is the insertion (seq, qual)[left, left + n) at key
@@ -2634,6 +3195,52 @@ extern "C" int mh_sam2aln_conc_counts(mh_ctx *ctx, int32_t *name_id, int64_t *po
         memcpy(counts5, Q.count.data(), sizeof(int32_t) * Q.count.size());
     }
     if (*read_n) memcpy(reads5, Q.reads.data(), sizeof(int64_t) * Q.reads.size());
+    return 0;
+}
+
+extern "C" int mh_sam2aln_strand(mh_ctx *ctx, char *buf, size_t cap, size_t *used)
+{
+    if (!ctx || !used) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_strand_of(ctx, "mh_sam2aln_strand", true, &S)) return st;
+    const std::string &t = S->strand.text;
+    *used = t.size();
+    if (!buf) return 0;
+    if (cap < t.size()) { set_error("mh_sam2aln_strand: buffer too small"); return -2; }
+    memcpy(buf, t.data(), t.size());
+    return 0;
+}
+
+extern "C" int mh_sam2aln_strand_write(mh_ctx *ctx, int fd, int64_t offset, int64_t *written)
+{
+    if (!ctx || fd < 0 || offset < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_strand_of(ctx, "mh_sam2aln_strand_write", true, &S)) return st;
+    const std::string &t = S->strand.text;
+    if (const int e = write_all_at(fd, t.data(), t.size(), offset)) {
+        set_error("mh_sam2aln_strand_write: write failed (%s)", strerror(e));
+        return -4;
+    }
+    if (written) *written = (int64_t)t.size();
+    return 0;
+}
+
+extern "C" int mh_sam2aln_strand_counts(mh_ctx *ctx, int32_t *name_id, int32_t *qcut, int64_t *pos,
+                                        int32_t *counts15, int64_t cap, int64_t *n)
+{
+    if (!ctx || !n || cap < 0) return -3;
+    S2AState *S = nullptr;
+    if (int st = s2a_strand_of(ctx, "mh_sam2aln_strand_counts", false, &S)) return st;
+    const S2AStrand &T = S->strand;
+    *n = (int64_t)T.name.size();
+    if (!name_id || !qcut || !pos || !counts15) return 0;
+    if (cap < *n) { set_error("mh_sam2aln_strand_counts: buffer too small"); return -2; }
+    if (*n) {
+        memcpy(name_id, T.name.data(), sizeof(int32_t) * T.name.size());
+        memcpy(qcut, T.qcut.data(), sizeof(int32_t) * T.qcut.size());
+        memcpy(pos, T.pos.data(), sizeof(int64_t) * T.pos.size());
+        memcpy(counts15, T.count.data(), sizeof(int32_t) * T.count.size());
+    }
     return 0;
 }
 

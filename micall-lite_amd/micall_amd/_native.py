@@ -158,6 +158,10 @@ def _declare(L):
                                          ctypes.c_int),
         'mh_sam2aln_conc_counts': ([_P, _P, _P, _P, ctypes.c_int64, _I64P, _P, ctypes.c_int64, _I64P],
                                    ctypes.c_int),
+        'mh_sam2aln_strand': ([_P, ctypes.c_char_p, ctypes.c_size_t,
+                               ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        'mh_sam2aln_strand_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
+        'mh_sam2aln_strand_counts': ([_P, _P, _P, _P, _P, ctypes.c_int64, _I64P], ctypes.c_int),
         'mh_sam2aln_conseq_ins': ([_P, ctypes.c_char_p, ctypes.c_size_t,
                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
         'mh_sam2aln_conseq_ins_write': ([_P, ctypes.c_int, ctypes.c_int64, _I64P], ctypes.c_int),
@@ -769,6 +773,42 @@ class Context:
                                                ctypes.byref(n), _ptr(reads), rn.value, ctypes.byref(rn)),
                   'mh_sam2aln_conc_counts')
         return ids, pos, cnt, reads
+
+    def sam2aln_strand(self):
+        """strand.csv text of the last sam2aln call (mh_sam2aln_strand): per
+        reference, q-cutoff, position and merged base the units whose
+        supporting mate is forward, reversed, and both.  The device pass runs
+        on the first request."""
+        used = ctypes.c_size_t()
+        check(lib().mh_sam2aln_strand(self.h, None, 0, ctypes.byref(used)), 'mh_sam2aln_strand')
+        buf = bytearray(used.value)
+        cbuf = (ctypes.c_char * len(buf)).from_buffer(buf)
+        check(lib().mh_sam2aln_strand(self.h, cbuf, len(buf), ctypes.byref(used)), 'mh_sam2aln_strand')
+        del cbuf
+        return buf.decode()
+
+    def sam2aln_strand_write(self, fd, offset):
+        """strand.csv written to fd at offset (pwrite); bytes written."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_strand_write(self.h, int(fd), int(offset), ctypes.byref(n)),
+              'mh_sam2aln_strand_write')
+        return n.value
+
+    def sam2aln_strand_counts(self):
+        """(name ids int32, cutoffs int32, positions int64, counts int32
+        [rows, 15]) of strand.csv's rows (mh_sam2aln_strand_counts); the
+        counts in the columns' order.  Name ids as in sam2aln_clip_counts."""
+        n = ctypes.c_int64()
+        check(lib().mh_sam2aln_strand_counts(self.h, None, None, None, None, 0, ctypes.byref(n)),
+              'mh_sam2aln_strand_counts')
+        ids = np.empty(n.value, dtype=np.int32)
+        cut = np.empty(n.value, dtype=np.int32)
+        pos = np.empty(n.value, dtype=np.int64)
+        cnt = np.empty((n.value, 15), dtype=np.int32)
+        if n.value:
+            check(lib().mh_sam2aln_strand_counts(self.h, _ptr(ids), _ptr(cut), _ptr(pos), _ptr(cnt), n.value,
+                                                 ctypes.byref(n)), 'mh_sam2aln_strand_counts')
+        return ids, cut, pos, cnt
 
     def sam2aln_conseq_ins(self):
         """conseq_ins.csv text of the last sam2aln call (mh_sam2aln_conseq_ins):

@@ -91,6 +91,8 @@ _SCHEMA = {
     'nuc_detail_ins': ['seed', 'region', 'q-cutoff', 'query.nuc.pos', 'refseq.nuc.pos'] + list('ACGT') +
                       ['N', 'del', 'clip', 'coverage', 'ins'],
     'nuc_detail_conc': ['overlap', 'mismatch', 'indel'],     # appended with concordance_csv
+    'nuc_detail_strand': ['A_fwd', 'A_rev', 'C_fwd', 'C_rev', 'G_fwd', 'G_rev', 'T_fwd', 'T_rev',
+                          'del_fwd', 'del_rev'],             # appended with strand_csv
     'amino_detail': ['seed', 'region', 'q-cutoff', 'query.aa.pos', 'refseq.aa.pos'] + list(AMINO_ALPHABET) +
                     ['X', 'partial', 'del', 'ins', 'clip', 'coverage'],
     'conseq': ['region', 'q-cutoff', 'consensus-percent-cutoff', 'offset', 'sequence'],
@@ -657,12 +659,15 @@ class SequenceReport(object):
     def write_amino_detail_header(self, amino_detail_file):
         _csv_writer(amino_detail_file, 'amino_detail').writeheader()
 
-    def write_nuc_detail_header(self, nuc_detail_file, insertions=False, concordance=False):
+    def write_nuc_detail_header(self, nuc_detail_file, insertions=False, concordance=False, strand=False):
         """insertions: the rows will end with the ins column; concordance:
-        with overlap, mismatch, indel after it."""
+        with overlap, mismatch, indel after it; strand: with the ten strand
+        columns after those."""
         fields = _SCHEMA['nuc_detail_ins' if insertions else 'nuc_detail']
         if concordance:
             fields = fields + _SCHEMA['nuc_detail_conc']
+        if strand:
+            fields = fields + _SCHEMA['nuc_detail_strand']
         csv.DictWriter(nuc_detail_file, fields, lineterminator=os.linesep).writeheader()
 
     # ---- bodies ----
@@ -751,7 +756,8 @@ class SequenceReport(object):
         positions when the seed has no coordinate region."""
         csv.writer(nuc_file, lineterminator=os.linesep).writerows(self._nuc_lines(4)[0])
 
-    def write_nuc_detail(self, nuc_detail_file, clipping=None, insertions=None, concordance=None):
+    def write_nuc_detail(self, nuc_detail_file, clipping=None, insertions=None, concordance=None,
+                         strand=None):
         """nuc.csv's rows (not in the reference) followed by what they leave
         out: the N and deletion counts of the position, the units that
         soft-clip it, and coverage = A + C + G + T + N + del, the depth
@@ -767,8 +773,13 @@ class SequenceReport(object):
         concordance.csv, None for none; with it every row ends (after ins)
         with the pairs whose mates both align the row's consensus position and
         those that disagree there on a base or on an indel, 0 without an
-        entry or a query position."""
+        entry or a query position.  strand: {seed: {(q-cutoff, consensus
+        position): the ten fwd and rev counts}} of sam2aln's strand.csv, None
+        for none; with it every row ends (after those) with A_fwd, A_rev, ...
+        del_fwd, del_rev of the row's consensus position at the row's cutoff,
+        0 without an entry or a query position."""
         lines, frames = self._nuc_lines(6)
+        strands = None if strand is None else strand.get(self.seed, {})
         concs = None if concordance is None else concordance.get(self.seed, {})
         clips = None if clipping is None else clipping.get(self.seed, {})
         inserts = None if insertions is None else insertions.get(self.seed, {})
@@ -780,6 +791,8 @@ class SequenceReport(object):
                 line.append(0 if query == '' else inserts.get((int(self.qcut), query - f), 0))
             if concs is not None:
                 line.extend((0, 0, 0) if query == '' else concs.get(query - f, (0, 0, 0)))
+            if strands is not None:
+                line.extend(_NO_STRAND if query == '' else strands.get((int(self.qcut), query - f), _NO_STRAND))
         csv.writer(nuc_detail_file, lineterminator=os.linesep).writerows(lines)
 
     def write_consensus(self, conseq_file, min_coverage=100):
@@ -1208,7 +1221,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                nuc_detail_csv=None, conseq_ins_csv=None, amino_detail_csv=None, linkage_csv=None,
                linkage_positions=None, linkage_min_count=1, concordance_csv=None, covariation_csv=None,
                covariation_min_fraction=0.01, covariation_min_count=10,
-               covariation_max_variants=COVARIATION_MAX_VARIANTS):
+               covariation_max_variants=COVARIATION_MAX_VARIANTS, strand_csv=None):
     """aligned.csv -> nucleotide, amino-acid, insertion, consensus (and the
     optional failure, variant and coverage) reports; every argument is an
     open file except json, a project-file path (None: the default).
@@ -1223,6 +1236,9 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
     concordance_csv is an input as well, sam2aln's concordance.csv: with it
     nuc_detail_csv's rows end with overlap, mismatch and indel, the pairs
     whose mates both align the position and those that disagree there.
+    strand_csv is an input too, sam2aln's strand.csv: with it nuc_detail_csv's
+    rows end with A_fwd, A_rev, ... del_fwd, del_rev, the units whose mate on
+    that strand supports the base at the position and the row's q-cutoff.
     amino_detail_csv takes amino.csv's rows with the X, partial, del, ins, clip
     and coverage columns (SequenceReport.write_amino_detail): the codons read
     at the position that amino.csv leaves out, counted on the device only
@@ -1302,7 +1318,8 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                             variants_csv=variants_csv, clipping_csv=clipping_csv,
                             nuc_detail_csv=nuc_detail_csv, conseq_ins_csv=conseq_ins_csv,
                             amino_detail_csv=amino_detail_csv, linkage_csv=linkage_csv, link=link,
-                            concordance_csv=concordance_csv, covariation_csv=covariation_csv, covar=covar)
+                            concordance_csv=concordance_csv, covariation_csv=covariation_csv, covar=covar,
+                            strand_csv=strand_csv)
             return
         # every rank builds the reports; the others' go nowhere
         outs = handles if stage.active else tuple(None if h is None else io.StringIO() for h in handles)
@@ -1315,7 +1332,7 @@ def aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv,
                         linkage_csv=None if job_link is None else outs[10] or io.StringIO(), link=job_link,
                         concordance_csv=concordance_csv,
                         covariation_csv=None if job_covar is None else outs[11] or io.StringIO(),
-                        covar=job_covar)
+                        covar=job_covar, strand_csv=strand_csv)
         finally:
             _SHARD = None
 
@@ -1379,7 +1396,7 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
                 nuc_variants_csv, callback, coverage_summary_csv, json, groups=None,
                 variants_csv=None, clipping_csv=None, nuc_detail_csv=None, conseq_ins_csv=None,
                 amino_detail_csv=None, job_detail=False, linkage_csv=None, link=None,
-                concordance_csv=None, covariation_csv=None, covar=None):
+                concordance_csv=None, covariation_csv=None, covar=None, strand_csv=None):
     projects = (project_config.ProjectConfig.loadDefault() if json is None
                 else project_config.ProjectConfig.loadCustom(json))
     report = SequenceReport(InsertionWriter(coord_ins_csv), projects, CONSEQ_MIXTURE_CUTOFFS)
@@ -1404,8 +1421,11 @@ def _aln2counts(aligned_csv, nuc_csv, amino_csv, coord_ins_csv, conseq_csv, fail
         insertions = None if conseq_ins_csv is None else _read_conseq_ins(conseq_ins_csv)
     if nuc_detail_csv is not None:
         concordance = None if concordance_csv is None else _read_concordance(concordance_csv)
-        report.write_nuc_detail_header(nuc_detail_csv, insertions is not None, concordance is not None)
-        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions, concordance))
+        strand = None if strand_csv is None else _read_strand(strand_csv)
+        report.write_nuc_detail_header(nuc_detail_csv, insertions is not None, concordance is not None,
+                                       strand is not None)
+        per_run.append(lambda: report.write_nuc_detail(nuc_detail_csv, clipping, insertions, concordance,
+                                                       strand))
     if amino_detail_csv is not None:
         report.write_amino_detail_header(amino_detail_csv)
         per_run.append(lambda: report.write_amino_detail(amino_detail_csv, clipping, insertions))
@@ -1479,6 +1499,18 @@ def _read_clipping(clipping_csv):
     return clipping
 
 
+_NO_STRAND = (0,) * 10
+
+
+def _read_strand(strand_csv):
+    """{refname: {(qcut, pos): (A_fwd, A_rev, C_fwd, ... del_fwd, del_rev)}} of sam2aln's strand.csv."""
+    strand = {}
+    for row in csv.DictReader(strand_csv):
+        strand.setdefault(row['refname'], {})[int(row['qcut']), int(row['pos'])] = tuple(
+            int(row[k]) for k in _SCHEMA['nuc_detail_strand'])
+    return strand
+
+
 def _read_concordance(concordance_csv):
     """{refname: {pos: (overlap, mismatch, indel)}} of sam2aln's concordance.csv."""
     concordance = {}
@@ -1520,6 +1552,8 @@ def _arguments(argv=None):
     cli.add_argument('--concordance_csv', type=argparse.FileType('r'),
                      help="input: sam2aln's concordance.csv, for the overlap, mismatch and indel "
                           "columns of nuc_detail_csv")
+    cli.add_argument('--strand_csv', type=argparse.FileType('r'),
+                     help="input: sam2aln's strand.csv, for the ten fwd and rev columns of nuc_detail_csv")
     cli.add_argument('--nuc_detail_csv', type=argparse.FileType('w'),
                      help='output: nuc.csv with N, deletion, soft-clip and coverage counts')
     cli.add_argument('--amino_detail_csv', type=argparse.FileType('w'),
@@ -1555,7 +1589,7 @@ def main():
                linkage_min_count=a.linkage_min_count, concordance_csv=a.concordance_csv,
                covariation_csv=a.covariation_csv, covariation_min_fraction=a.covariation_min_fraction,
                covariation_min_count=a.covariation_min_count,
-               covariation_max_variants=a.covariation_max_variants)
+               covariation_max_variants=a.covariation_max_variants, strand_csv=a.strand_csv)
 
 
 if __name__ == '__main__':

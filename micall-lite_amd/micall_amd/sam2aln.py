@@ -57,6 +57,17 @@ with no phiX.  A cycle is the base's place in the read as the FASTQ held
 it, so after trim_fastqs it counts from the trimmed 5' end.  Counted on
 the device like the clipping (mh_sam2aln_concordance: k_s2a_conc,
 k_s2a_conc_scan), once for both files and only when asked for.
+
+strand_csv (optional, not in the reference): which strand saw each merged
+base.  A unit counts at the cutoffs at which it gives aligned.csv a sequence.
+At position y with merged base m (A, C, G, T or '-'), a mate supports m
+when its own expansion holds m at y, whatever its quality; the unit adds 1
+to m_fwd when a supporting mate is forward (FLAG 0x10 clear), 1 to m_rev
+when one is reversed, and 1 to m_both when both hold: refname,qcut,pos and
+the fifteen counts, so that fwd + rev - both is the number of aligned.csv's
+sequences (by count) that hold m there.  Counted on the device like the
+clipping (mh_sam2aln_strand: k_s2a_strand, k_s2a_strand_scan), once for all
+the cutoffs and only when asked for.
 """
 import argparse
 import os
@@ -90,7 +101,8 @@ def _cutoff_list(q_cutoffs):
 
 
 def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=None, q_cutoffs=None,
-            clipping_csv=None, conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None):
+            clipping_csv=None, conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None,
+            strand_csv=None):
     """sam2aln.sam2aln (sam2aln.py:395-478).  q_cutoffs: the list of quality
     cutoffs, None for the module's SAM2ALN_Q_CUTOFFS (where the reference's
     users set it).  In a sharded job every rank does its share
@@ -99,7 +111,8 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     clipping_csv: an open file for the soft-clip counts, None for none;
     conseq_ins_csv: one for the merged insertions; concordance_csv and
     cycle_concordance_csv: one each for the mates' concordance per consensus
-    position and per read cycle and quality."""
+    position and per read cycle and quality; strand_csv: one for the strand
+    support of every merged base."""
     cuts = _cutoff_list(q_cutoffs)
     sh = session.shard()
     SHARD_STATS.clear()
@@ -108,10 +121,11 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
     use_resident = os.environ.get('MICALL_SAM2ALN_RESIDENT', '1') != '0'
     if sh is not None and _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts,
                                            clipping_csv, conseq_ins_csv, concordance_csv,
-                                           cycle_concordance_csv):
+                                           cycle_concordance_csv, strand_csv):
         return
     with session.writer_stage(aligned_csv, insert_csv, failed_csv, clipping_csv,
-                              conseq_ins_csv, concordance_csv, cycle_concordance_csv) as stage:
+                              conseq_ins_csv, concordance_csv, cycle_concordance_csv,
+                              strand_csv) as stage:
         if not stage.active:
             return
         ctx = session.context()
@@ -137,6 +151,8 @@ def sam2aln(remap_csv, aligned_csv, insert_csv=None, failed_csv=None, nthreads=N
             if handle:
                 _write_side(handle, lambda fd, at, w=which: ctx.sam2aln_concordance_write(w, fd, at),
                             lambda w=which: ctx.sam2aln_concordance(w))
+        if strand_csv:
+            _write_side(strand_csv, ctx.sam2aln_strand_write, ctx.sam2aln_strand)
         for which, handle in (('insert', insert_csv), ('failed', failed_csv), ('aligned', aligned_csv)):
             if handle:
                 start = _write_output(ctx, which, handle)
@@ -148,7 +164,8 @@ SAMPLES_PER_NAME = 64   # sample records per reference and rank for the splitter
 
 
 def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=None, clipping_csv=None,
-                     conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None):
+                     conseq_ins_csv=None, concordance_csv=None, cycle_concordance_csv=None,
+                     strand_csv=None):
     """This rank's share of sam2aln.  False (on every rank, before any
     output is written) when the job must fall back to rank 0 alone: more
     than one q-cutoff (every rank holds the same list, so none has to ask),
@@ -184,6 +201,8 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
         _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv)
     if concordance_csv or cycle_concordance_csv:
         _concordance_sharded(sh, ctx, names, concordance_csv, cycle_concordance_csv)
+    if strand_csv:
+        _strand_sharded(sh, ctx, names, cuts, strand_csv)
     texts = sh.all_gather_bytes('\n'.join(names).encode())
     firsts = sh.all_gather_bytes(np.asarray(first, dtype=np.int64).tobytes())
     pairs = sh._gather_sizes([part['pair_units']])[:, 0]
@@ -231,7 +250,7 @@ def _sam2aln_sharded(sh, remap_csv, aligned_csv, insert_csv, failed_csv, cuts=No
     out.finish()
     sh.barrier()             # every rank's rows are in the files
     for h in (aligned_csv, insert_csv, failed_csv, clipping_csv, conseq_ins_csv, concordance_csv,
-              cycle_concordance_csv):
+              cycle_concordance_csv, strand_csv):
         if h and sh.rank == 0:
             h.flush()
     return True
@@ -297,6 +316,36 @@ def _concordance_sharded(sh, ctx, names, concordance_csv, cycle_concordance_csv)
         w.writerow(CYCLE_CONCORDANCE_HEADER)
         w.writerows((read, 'quality' if by else 'cycle', value) + table[read, by, value]
                     for read, by, value in sorted(table))
+
+
+STRAND_HEADER = ['refname', 'qcut', 'pos'] + [base + strand for base in ('A', 'C', 'G', 'T', 'del')
+                                              for strand in ('_fwd', '_rev', '_both')]
+
+
+def _strand_sharded(sh, ctx, names, cuts, strand_csv):
+    """strand.csv of a sharded call: every rank counts its own units on its
+    device, the rows are all-gathered, and rank 0 sums them and writes in the
+    file's order (names as str sorts, the call's cutoffs, positions), as
+    _concordance_sharded does."""
+    import csv
+    ids, cut, pos, cnt = ctx.sam2aln_strand_counts()
+    mine = '\n'.join(names).encode(), ids.tobytes(), cut.tobytes(), pos.tobytes(), cnt.tobytes()
+    parts = [sh.all_gather_bytes(x) for x in mine]
+    if sh.rank != 0:
+        return
+    total = {}
+    for r in range(sh.world):
+        rn = parts[0][r].decode().split('\n') if parts[0][r] else []
+        for i, q, p, fifteen in zip(np.frombuffer(parts[1][r], dtype=np.int32).tolist(),
+                                    np.frombuffer(parts[2][r], dtype=np.int32).tolist(),
+                                    np.frombuffer(parts[3][r], dtype=np.int64).tolist(),
+                                    np.frombuffer(parts[4][r], dtype=np.int32).reshape(-1, 15).tolist()):
+            key = rn[i], q, p
+            total[key] = [a + b for a, b in zip(total[key], fifteen)] if key in total else fifteen
+    w = csv.writer(strand_csv, lineterminator='\n')
+    w.writerow(STRAND_HEADER)
+    w.writerows([name, q, p] + total[name, q, p]
+                for name, q, p in sorted(total, key=lambda k: (k[0], cuts.index(k[1]), k[2])))
 
 
 def _conseq_ins_sharded(sh, ctx, cuts, conseq_ins_csv):
@@ -391,6 +440,9 @@ def parseArgs():
                         metavar='FILE',
                         help='<output> CSV of the bases compared with the mate and found different, '
                              'per read and sequencing cycle and per read and quality')
+    parser.add_argument('--strand_csv', type=argparse.FileType('w'), default=None, metavar='FILE',
+                        help='<output> CSV of the strand support of every merged base: per position '
+                             'and base the pairs with a supporting mate forward, reversed and both')
     return parser.parse_args()
 
 
@@ -399,7 +451,8 @@ def main():
     sam2aln(remap_csv=args.remap_csv, aligned_csv=args.aligned_csv, insert_csv=args.insert_csv,
             failed_csv=args.failed_csv, nthreads=args.p, q_cutoffs=args.qcut,
             clipping_csv=args.clipping_csv, conseq_ins_csv=args.conseq_ins_csv,
-            concordance_csv=args.concordance_csv, cycle_concordance_csv=args.cycle_concordance_csv)
+            concordance_csv=args.concordance_csv, cycle_concordance_csv=args.cycle_concordance_csv,
+            strand_csv=args.strand_csv)
 
 
 if __name__ == '__main__':
